@@ -8,6 +8,12 @@ CXXFLAGS := -O3 -std=c++17 -fPIC -fvisibility=hidden -Iinclude -I$(CSRC) -Wno-un
 OBJS := build/obj/api.o build/obj/planner.o build/obj/kernels.o build/obj/kernels_pow2.o build/obj/kernels_blue_r2r.o build/obj/kernels_fused.o build/obj/kernels_mixfused.o build/obj/kernels_aux.o build/obj/kernels_mixed_0.o build/obj/kernels_mixed_1.o build/obj/kernels_mixed_2.o build/obj/kernels_mixed_3.o build/obj/kernels_mixed_4.o build/obj/kernels_mixed_5.o build/obj/kernels_mixed_6.o build/obj/kernels_mixed_7.o build/obj/kernels_mixed_8.o build/obj/kernels_mixed_9.o build/obj/kernels_mixed_10.o build/obj/kernels_mixed_11.o build/obj/kernels_mixed_12.o build/obj/kernels_mixed_13.o build/obj/kernels_mixed_14.o build/obj/kernels_mixed_15.o build/obj/kernels_mixed_16.o build/obj/kernels_mixed_17.o build/obj/kernels_mixed_18.o build/obj/kernels_mixed_19.o \
         build/obj/kernels_mixconv_0.o build/obj/kernels_mixconv_1.o build/obj/kernels_mixconv_2.o build/obj/kernels_mixconv_3.o build/obj/kernels_mixconv_4.o build/obj/kernels_mixconv_5.o \
         $(foreach t,f32_row f32_col f64_row f64_col,build/obj/kernels_opfft_$(t)_0.o build/obj/kernels_opfft_$(t)_1.o) build/obj/kernels_opfft_f32_col_2.o
+# the translation units that take longest to compile (12 minutes each for kernels_mixed_0 ... 5, 4-6 for the others; the rest 2 minutes or less), named first among the
+# library's prerequisites so that a parallel make starts them first and no core waits for one of them at the end; the link line keeps the order of OBJS
+LONG_OBJS := $(foreach i,0 1 2 3 4 5,build/obj/kernels_mixed_$(i).o) build/obj/kernels_mixconv_4.o build/obj/kernels_mixconv_0.o build/obj/kernels_mixconv_2.o \
+        build/obj/kernels_opfft_f32_col_0.o build/obj/kernels_opfft_f32_col_1.o build/obj/kernels_mixconv_1.o build/obj/kernels_mixconv_3.o build/obj/kernels_mixconv_5.o \
+        build/obj/kernels_opfft_f32_row_0.o build/obj/kernels_opfft_f32_row_1.o
+# every rule names what it starts, so that a silent (-s) build of half an hour still shows where it stands
 # header dependencies come from the compiler (-MMD): a change to one kernel family rebuilds only the translation units that include it
 DEPFLAGS = -MMD -MP -MF build/obj/$*.d
 
@@ -26,14 +32,17 @@ build/vkfft_mi355x_multi: tools/vkfft_multi.cpp include/vkFFT.h $(LIBDIR)/libvkf
 
 build/obj/%.o: $(CSRC)/%.cpp
 	@mkdir -p build/obj
+	@echo "  HIPCC  $<"
 	$(HIPCC) $(CXXFLAGS) $(DEPFLAGS) --offload-arch=$(ARCH) -c $< -o $@
 
 build/obj/%.o: $(CSRC)/%.hip
 	@mkdir -p build/obj
+	@echo "  HIPCC  $<"
 	$(HIPCC) $(CXXFLAGS) $(DEPFLAGS) --offload-arch=$(ARCH) -c $< -o $@
 
-$(LIBDIR)/libvkfft_mi355x.so: $(OBJS)
+$(LIBDIR)/libvkfft_mi355x.so: $(LONG_OBJS) $(OBJS)
 	@mkdir -p $(LIBDIR)
+	@echo "  LINK   $@"
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) $(OBJS) -o $@
 
 # development build of the fused Four-Step kernels (per-phase cycle profile, arithmetic-free variants): tools/prof_fused.py,

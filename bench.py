@@ -12,10 +12,16 @@ to inf/NaN as it does in the reference's unnormalised loop (data-dependent clock
 Multi-GPU: the batch axis is sharded, every rank owns an independent 1 GiB buffer ("weak" scaling), no
 collective on the data path; ranks only meet in the barrier around the timed region.
 
-Prints ONE JSON line on rank 0.  Extra objects:
-  roofline     : dominant kernel of the sweep, algorithmic bytes per launch / HIP-event launch duration
-  cpu_baseline : the reference's CPU path (FFTW3 API, served by MKL) timed on this box's host cores on a
-                 bounded sample of the same workload
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times `--steps` steps and prints the headline
+figure (`value`, `ms_per_step`); nothing else runs.
+  --dump-outputs DIR : after the timed steps, write what the timed path left for its caller in the last step as
+                       DIR/<name>.npy (float32; a fixed, seeded sample of the 1 GiB buffer, see dump_outputs)
+  --full             : everything else the benchmark measures or checks, after the timed steps:
+      round trip   : the buffer against its initial contents (every pair is FFT + normalised inverse); fails the run
+      per_size     : HIP-event time of every size's pair, forward-only rate
+      roofline     : dominant kernel of the sweep, algorithmic bytes per launch / HIP-event launch duration
+      cpu_baseline : the reference's CPU path (FFTW3 API, served by MKL) timed on this box's host cores on a
+                     bounded sample of the same workload
 """
 import argparse
 import json
@@ -61,7 +67,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--full", action="store_true", help="also run the round-trip check, the per-size table, the roofline and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/<name>.npy")
     ap.add_argument("--workload", default="c2c-sweep", choices=["c2c-sweep", "slab3d"])
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -105,7 +113,8 @@ def main():
             apps[k].forward()
             apps[k].inverse()
 
-    initial = buf.clone()  # every pair is FFT followed by the normalised inverse: the buffer must come back (checked after the timed region)
+    # every pair is FFT followed by the normalised inverse: the buffer must come back (--full: checked after the timed region)
+    initial = buf.clone() if args.full else None
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
@@ -120,7 +129,74 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    # ---- result check of the timed work itself: (warmup + steps) x 15 forward/inverse pairs later the buffer is its initial contents up to rounding
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, buf, apps, rank, world)
+    if dist:
+        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    ms_per_step = 1e3 * elapsed / args.steps
+    total_flops = sum(flops_pair(k) for k in range(KMIN, KMAX + 1)) * world
+    bytes_step = (KMAX - KMIN + 1) * 2 * 2 * (8 << TOTAL_LOG2) * world  # 15 sizes x (fwd+inv) x (read+write) x 1 GiB
+    value = total_flops / (ms_per_step * 1e-3) / 1e9
+
+    extras = {}
+    if args.full:
+        extras = full_measurements(args, torch, api, dist, buf, initial, apps, gen, dev, stream, rank, world)
+    for a in apps.values():
+        a.delete()
+    if rank == 0:
+        out = dict(metric="GFLOP/s (5N log2 N) + achieved HBM GB/s, batched 1D C2C fp32, 1/2/4/8 GPU", value=round(value, 1),
+                   unit="GFLOP/s", n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=round(ms_per_step, 4),
+                   higher_is_better=True, scaling="weak", vs_baseline=None, dtype="f32", data="synthetic",
+                   config=dict(workload="batched 1D C2C fp32 in-place, N=2^8..2^22, batch=2^27/N (1 GiB per GPU), FFT+iFFT pair per size per step (sample-0 protocol)",
+                               sizes_log2=[KMIN, KMAX], buffer_bytes_per_gpu=8 << TOTAL_LOG2, parallelism=f"batch-sharded x{world}, no collectives",
+                               source_hash=api.source_hash(), library_newer_than_sources=bool(api.library_is_current())),
+                   alg_GBps=round(bytes_step / (ms_per_step * 1e-3) / 1e9, 1), full=bool(args.full), **extras)
+        print(json.dumps(out))
+    if dist:
+        dist.destroy_process_group()
+
+
+DUMP_SEED = 20240229
+DUMP_BUFFER_POINTS = 1 << 21   # complex points sampled from the buffer after the last timed step (16 MiB as float32 pairs)
+DUMP_SPECTRUM_POINTS = 1 << 18  # complex points sampled from every size's forward spectrum (15 x 2 MiB)
+
+
+def dump_sample(dirname, name, torch, cplx, idx):
+    """DIR/<name>.npy: the complex points `idx` of the flat complex tensor `cplx` as a float32 array of (re, im) rows"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    a = torch.view_as_real(cplx.reshape(-1)[idx]).cpu().numpy().astype(np.float32, copy=False)
+    np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def dump_outputs(dirname, torch, buf, apps, rank, world):
+    """What the timed path left for its caller, as DIR/<name>.npy (float32, 46 MiB in all; ranks above 0 add `_rank<r>` to the names):
+      buffer_after_last_step : the in-place buffer as the last timed step left it (every step ends on a normalised inverse), a fixed sample of its 2^27 points
+      spectrum_log2N_<k>     : the forward transform of size 2^k of that buffer, the intermediate result a caller of the same plan receives; taken in one more,
+                               untimed, pass over the sizes (the timed steps are not touched), after which the buffer is put back as the last step left it
+    The sampled positions come from a seeded generator and depend on nothing else, and the input buffer is seeded: two builds run with the same arguments
+    write arrays that can be compared element for element."""
+    import numpy as np
+    sfx = f"_rank{rank}" if world > 1 else ""
+    rng = np.random.default_rng(DUMP_SEED)
+    npoints = 1 << TOTAL_LOG2
+    cplx = torch.view_as_complex(buf.view(-1, 2))
+    idx = torch.from_numpy(np.sort(rng.integers(0, npoints, DUMP_BUFFER_POINTS))).to(buf.device)
+    dump_sample(dirname, "buffer_after_last_step" + sfx, torch, cplx, idx)
+    last = buf.clone()
+    for k in sorted(apps):
+        idx = torch.from_numpy(np.sort(rng.integers(0, npoints, DUMP_SPECTRUM_POINTS))).to(buf.device)
+        apps[k].forward()
+        torch.cuda.synchronize()
+        dump_sample(dirname, f"spectrum_log2N_{k}" + sfx, torch, cplx, idx)
+        buf.copy_(last)
+    torch.cuda.synchronize()
+
+
+def roundtrip_check(args, torch, dist, buf, initial):
+    """--full: result check of the timed work itself: (warmup + steps) x 15 forward/inverse pairs later the buffer is its initial contents up to rounding"""
     diff = buf - initial
     roundtrip_rel_l2 = float(torch.linalg.vector_norm(diff.double()) / torch.linalg.vector_norm(initial.double()))
     max_abs_err = float(diff.abs().max())
@@ -139,16 +215,12 @@ def main():
     if not finite or not (roundtrip_rel_l2 <= rt_limit) or not (max_abs_err <= 8 * rt_limit):
         raise SystemExit(f"bench.py: result check failed after the timed loop: round-trip rel. L2 {roundtrip_rel_l2:.3e} (limit {rt_limit:.3e}), "
                          f"max |err| {max_abs_err:.3e}, finite={finite}")
-    if dist:
-        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-    ms_per_step = 1e3 * elapsed / args.steps
-    total_flops = sum(flops_pair(k) for k in range(KMIN, KMAX + 1)) * world
-    bytes_step = (KMAX - KMIN + 1) * 2 * 2 * (8 << TOTAL_LOG2) * world  # 15 sizes x (fwd+inv) x (read+write) x 1 GiB
-    value = total_flops / (ms_per_step * 1e-3) / 1e9
+    return dict(roundtrip_rel_l2=float(f"{roundtrip_rel_l2:.3e}"), max_abs_err=float(f"{max_abs_err:.3e}"), roundtrip_limit_rel_l2=float(f"{rt_limit:.3e}"),
+                roundtrip_pairs=pairs)
 
-    # ---- per-size table + dominant kernel, HIP events on the launch stream (outside the contract-timed region) ----
+
+def per_size_and_roofline(torch, api, buf, apps, gen, dev, stream):
+    """--full: per-size table + dominant kernel, HIP events on the launch stream (outside the contract-timed region)"""
     GIB2 = 2.0 * (8 << TOTAL_LOG2)  # algorithmic bytes of one transform of the buffer: one read + one write
     per_size = {}
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -228,27 +300,19 @@ def main():
         else:
             roofline["traffic_source"] = f"null: {os.path.basename(prof)} holds no counters for the instance launched at 2^{kd}"
         break
+    return dict(per_size=per_size, roofline=roofline)
 
+
+def full_measurements(args, torch, api, dist, buf, initial, apps, gen, dev, stream, rank, world):
+    """--full: what the benchmark measures or checks beside its headline figure; returns the extra fields of the result line"""
+    extras = roundtrip_check(args, torch, dist, buf, initial)
+    extras.update(per_size_and_roofline(torch, api, buf, apps, gen, dev, stream))
     # ---- CPU baseline (rank 0, N=1 only) ------------------------------------------------------------------------
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline()
-
-    for a in apps.values():
-        a.delete()
-    if rank == 0:
-        out = dict(metric="GFLOP/s (5N log2 N) + achieved HBM GB/s, batched 1D C2C fp32, 1/2/4/8 GPU", value=round(value, 1),
-                   unit="GFLOP/s", n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=round(ms_per_step, 4),
-                   higher_is_better=True, scaling="weak", vs_baseline=None, dtype="f32", data="synthetic",
-                   config=dict(workload="batched 1D C2C fp32 in-place, N=2^8..2^22, batch=2^27/N (1 GiB per GPU), FFT+iFFT pair per size per step (sample-0 protocol)",
-                               sizes_log2=[KMIN, KMAX], buffer_bytes_per_gpu=8 << TOTAL_LOG2, parallelism=f"batch-sharded x{world}, no collectives",
-                               source_hash=api.source_hash(), library_newer_than_sources=bool(api.library_is_current())),
-                   alg_GBps=round(bytes_step / (ms_per_step * 1e-3) / 1e9, 1),
-                   roundtrip_rel_l2=float(f"{roundtrip_rel_l2:.3e}"), max_abs_err=float(f"{max_abs_err:.3e}"), roundtrip_limit_rel_l2=float(f"{rt_limit:.3e}"),
-                   roundtrip_pairs=pairs, per_size=per_size, roofline=roofline, cpu_baseline=cpu)
-        print(json.dumps(out))
-    if dist:
-        dist.destroy_process_group()
+    extras["cpu_baseline"] = cpu
+    return extras
 
 
 def slab3d_main(args):
@@ -280,6 +344,10 @@ def slab3d_main(args):
         x = step(x)
     torch.cuda.synchronize(); dist.barrier(); torch.cuda.synchronize()
     t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device="cuda")
+    if args.dump_outputs:  # this rank's slab of the volume after the last step: a fixed, seeded sample of its points
+        import numpy as np
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, x.numel(), min(DUMP_BUFFER_POINTS, x.numel())))
+        dump_sample(args.dump_outputs, "volume_after_last_step" + (f"_rank{rank}" if world > 1 else ""), torch, x, torch.from_numpy(idx).to(x.device))
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     ms = 1e3 * float(t.item()) / args.steps
     import math

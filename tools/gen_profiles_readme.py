@@ -3,7 +3,8 @@
 sections stay in the README as written).  usage: python tools/gen_profiles_readme.py r06 [previous round tag, default: the one before]
 Refuses to run when the bench line, the kernel stats and the PMC summary were not taken on the same sources; the reference column comes ONLY from
 `<tag>_reference_pow2_same_lease.jsonl` (the reference's own sweep run in the same gpurun call as the bench line: the boxes of the pool differ by 3-4 %).  The traffic of
-the roofline's instance is read from the PMC summary (`by_log2N`), not from the bench line (which may have been written before the counters existed)."""
+the roofline's instance is read from the PMC summary (`by_log2N`), not from the bench line (which may have been written before the counters existed).
+`<tag>_bench.json` is the line of `python bench.py --full` (the per-size table and the roofline are read from it)."""
 import collections, glob, json, math, os, re, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = os.path.join(ROOT, "profiles")
