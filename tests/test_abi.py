@@ -96,17 +96,24 @@ def test_public_header_compiles_as_c99():
 
 
 def test_environment_switches_are_documented():
-    """every VKFFT_MI355X_* name the library reads (literal getenv calls in vkfft_amd/csrc) appears in INTEGRATION.md's switch table — by its full name or by the
-    abbreviated `_SUFFIX` form the table uses inside a family — and the table names no switch the sources do not read"""
+    """every VKFFT_MI355X_* name of the library's switch table (vkfft_amd/csrc/switches.h, the only file that reads the environment) appears in INTEGRATION.md's switch
+    table — by its full name or by the abbreviated `_SUFFIX` form the table uses inside a family; an indexed family NAME<k> by `NAME<k>` — and the document names no
+    switch the table lacks"""
     import glob, re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = "".join(open(f, errors="replace").read() for f in glob.glob(os.path.join(root, "vkfft_amd", "csrc", "*")) if f.endswith((".cpp", ".hip", ".h")))
-    read = set(re.findall(r'getenv\("(VKFFT_MI355X_[A-Z0-9_]+)"\)', src))
+    csrc = os.path.join(root, "vkfft_amd", "csrc")
+    readers = sorted(os.path.basename(f) for f in glob.glob(os.path.join(csrc, "*")) if os.path.isfile(f) and "getenv(" in open(f, errors="replace").read())
+    assert readers == ["switches.h"], readers
+    src = open(os.path.join(csrc, "switches.h")).read()
+    plain = set(re.findall(r"^\s*X\((VKFFT_MI355X_[A-Z0-9_]+),", src, re.M))
+    indexed = set(re.findall(r"^\s*XI\((VKFFT_MI355X_[A-Z0-9_]+),", src, re.M))
+    assert len(plain) >= 36 and indexed == {"VKFFT_MI355X_P2V", "VKFFT_MI355X_P2C", "VKFFT_MI355X_P2B", "VKFFT_MI355X_FUV"}, (plain, indexed)
     doc = open(os.path.join(root, "INTEGRATION.md")).read()
     table = doc[doc.index("## Environment switches"):doc.index("## FFI stubs")]
-    missing = [n for n in sorted(read) if n not in table and ("`" + n[len("VKFFT_MI355X"):]) not in table]
+    short = lambda n: "`" + n[len("VKFFT_MI355X"):]
+    missing = [n for n in sorted(plain) if n not in table and short(n) not in table]
+    missing += [n for n in sorted(indexed) if n + "<k>" not in table and short(n) + "<k>" not in table]
     assert not missing, missing
     named = set(re.findall(r"VKFFT_MI355X_[A-Z0-9_]+", table))
-    built = {"VKFFT_MI355X_P2V", "VKFFT_MI355X_FUV", "VKFFT_MI355X_LIB"}  # (names assembled at run time: P2V<k>, FUV<k>; the Python stub's own)
-    stale = [n for n in sorted(named) if n not in read and n not in built and not any(r.startswith(n) for r in read)]
+    stale = [n for n in sorted(named) if n not in plain | indexed | {"VKFFT_MI355X_LIB"}]  # (VKFFT_MI355X_LIB: the Python stub's own)
     assert not stale, stale

@@ -74,7 +74,7 @@ VkFFTResult make_direction(VkFFTApplication* app, const TransformDesc& base, boo
 	return VKFFT_SUCCESS;
 }
 
-VkFFTResult initialize_convolution(VkFFTApplication* app, const VkFFTConfiguration& in);
+VkFFTResult initialize_convolution(VkFFTApplication* app, const VkFFTConfiguration& in, const Switches& sw);
 VkFFTResult append_convolution(VkFFTApplication* app, int inverse, VkFFTLaunchParams* lp);
 VkFFTResult zero_padded_ranges(VkFFTApplication* app, bool inverse, void* base, hipStream_t stream);
 
@@ -183,7 +183,8 @@ VKFFT_API VkFFTResult initializeVkFFT(VkFFTApplication* app, VkFFTConfiguration 
 		fprintf(stderr, "vkfft_mi355x: %s is outside the scope of this library (see DESIGN.md)\n", what);
 		return VKFFT_ERROR_PLAN_NOT_INITIALIZED;
 	};
-	if (in.performConvolution) return initialize_convolution(app, in);
+	const Switches sw = read_switches(); // the one look at the environment: everything below, the planner and the launches take the switches from here
+	if (in.performConvolution) return initialize_convolution(app, in, sw);
 	if (in.bufferNum > 1 || in.inputBufferNum > 1 || in.outputBufferNum > 1 || in.tempBufferNum > 1 || in.kernelNum > 1) return unsupported("a buffer split over several allocations (bufferNum > 1)");
 	bool zeroPad = false;
 	for (pfUINT i = 0; i < in.FFTdim; i++) if (in.performZeropadding[i]) {
@@ -252,7 +253,7 @@ VKFFT_API VkFFTResult initializeVkFFT(VkFFTApplication* app, VkFFTConfiguration 
 	// request is not honoured, and the caller is TOLD so: the application's own copy of the configuration reports what is in effect (reorder on, flag cleared);
 	// printMemoryLayout / VKFFT_MI355X_PRINT_PLAN print a line.  Natural order is one valid instance of the unspecified order for every forward -> pointwise ->
 	// inverse pipeline whose operands all come from this library.
-	if (in.disableReorderFourStep && (in.printMemoryLayout || getenv("VKFFT_MI355X_PRINT_PLAN")))
+	if (in.disableReorderFourStep && (in.printMemoryLayout || sw.printPlan))
 		fprintf(stderr, "[vkfft_mi355x] disableReorderFourStep requested: not applied, results stay in natural order (app->configuration.disableReorderFourStep reads back 0)\n");
 	c.reorderFourStep = 1; c.disableReorderFourStep = 0;
 	if (in.userTempBuffer) {
@@ -290,22 +291,14 @@ VKFFT_API VkFFTResult initializeVkFFT(VkFFTApplication* app, VkFFTConfiguration 
 	if (c.userTempBuffer && c.tempBufferSize) d.userTempBytes = c.tempBufferSize[0];
 	for (pfUINT i = 0; i < c.FFTdim && i < 4; i++) if (c.performZeropadding[i] && c.fft_zeropad_right[i] > c.fft_zeropad_left[i]) { d.padL[i] = c.fft_zeropad_left[i]; d.padR[i] = c.fft_zeropad_right[i]; }
 	d.padFrequency = c.frequencyZeroPadding != 0;
-	// fused Four-Step tuning knobs (experiments only; defaults are the planner's)
-	if (const char* e = getenv("VKFFT_MI355X_FUSED")) d.fused = atoi(e) != 0;
-	if (const char* e = getenv("VKFFT_MI355X_FUSED_MODE")) d.fusedMode = atoi(e);
-	if (const char* e = getenv("VKFFT_MI355X_FUSED_CHUNK_KIB")) d.fusedChunkBytes = (uint64_t)atoll(e) << 10;
-	if (const char* e = getenv("VKFFT_MI355X_FUSED_LAG")) d.fusedLag = (uint32_t)atoi(e);
-	if (const char* e = getenv("VKFFT_MI355X_FUSED_RING")) d.fusedRing = (uint32_t)atoi(e);
-	if (const char* e = getenv("VKFFT_MI355X_FUSED_WGS")) d.fusedWgPerCu = (uint32_t)atoi(e);
-	if (const char* e = getenv("VKFFT_MI355X_FUSED_QUEUES")) d.fusedQueues = (uint32_t)atoi(e);
-	if (const char* e = getenv("VKFFT_MI355X_FUSED_MARGIN")) d.fusedMarginPct = (uint32_t)atoi(e);
-	if (const char* e = getenv("VKFFT_MI355X_GENERIC_ONLY")) d.disableFastKernels = atoi(e) != 0;
+	d.sw = sw;
+	d.disableFastKernels = sw.genericOnly;
 	if (ldsCapped) d.disableFastKernels = true; // the hand-specialised kernels have fixed LDS footprints (up to 155 KiB): under a cap the generic kernel, which sizes its tiles from maxLds, serves the plan
 
 	AppState* st = new (std::nothrow) AppState();
 	if (!st) { memset(app, 0, sizeof(*app)); return VKFFT_ERROR_MALLOC_FAILED; }
 	app->impl = st;
-	st->sweepEnabled = getenv("VKFFT_MI355X_NO_REVERSE") == nullptr;
+	st->sweepEnabled = !sw.noReverse;
 
 	VkFFTResult res = VKFFT_SUCCESS;
 	if (!c.makeForwardPlanOnly) {
@@ -326,7 +319,7 @@ VKFFT_API VkFFTResult initializeVkFFT(VkFFTApplication* app, VkFFTConfiguration 
 			return unsupported("zero-padding of a separate input buffer on an axis whose plan cannot skip the padded range (several passes, Bluestein, R2R)");
 		}
 	}
-	if (c.printMemoryLayout || getenv("VKFFT_MI355X_PRINT_PLAN")) { // one line per launch: which kernel family serves it
+	if (c.printMemoryLayout || sw.printPlan) { // one line per launch: which kernel family serves it
 		static const char* kname[] = {"generic", "pow2_row", "pow2_col", "r2c_pair", "?", "mixed_row", "opfft", "pow2_blue", "pow2_col_blue", "pow2_blue_r2r", "pow2_fused", "transpose", "real_map", "mixconv", "mix_fused"};
 		for (int dir = 0; dir < 2; dir++) {
 			VkFFTPlan* pl = dir ? app->localFFTPlan_inverse : app->localFFTPlan;
@@ -498,7 +491,7 @@ VkFFTResult zero_padded_ranges(VkFFTApplication* app, bool inverse, void* base, 
 	return VKFFT_SUCCESS;
 }
 
-VkFFTResult initialize_convolution(VkFFTApplication* app, const VkFFTConfiguration& in) {
+VkFFTResult initialize_convolution(VkFFTApplication* app, const VkFFTConfiguration& in, const Switches& sw) {
 	auto unsupported = [&](const char* what) {
 		fprintf(stderr, "vkfft_mi355x: convolution with %s is outside the scope of this library (see DESIGN.md)\n", what);
 		return VKFFT_ERROR_PLAN_NOT_INITIALIZED;
@@ -518,7 +511,7 @@ VkFFTResult initialize_convolution(VkFFTApplication* app, const VkFFTConfigurati
 	c.matrixConvolution = m; c.numberKernels = nk; c.numberBatches = nb;
 	c.coordinateFeatures = m > 1 ? m : (in.coordinateFeatures ? in.coordinateFeatures : 1); // reference: vkFFT_InitializeApp.h:1374
 	// (as for plain applications, setConfigurationVkFFT: the flag is reported back as not applied — and the notice is printed once, not by the sub-applications too)
-	if (in.disableReorderFourStep && (in.printMemoryLayout || getenv("VKFFT_MI355X_PRINT_PLAN")))
+	if (in.disableReorderFourStep && (in.printMemoryLayout || sw.printPlan))
 		fprintf(stderr, "[vkfft_mi355x] disableReorderFourStep requested: not applied, results stay in natural order (app->configuration.disableReorderFourStep reads back 0)\n");
 	c.reorderFourStep = 1; c.disableReorderFourStep = 0;
 	app->actualNumBatches = nb;
@@ -536,7 +529,7 @@ VkFFTResult initialize_convolution(VkFFTApplication* app, const VkFFTConfigurati
 	if (nk > 1 && in.bufferSize) b.bufferSize = in.bufferSize;
 	// merged last axis (the reference's convolution-merged kernel, vkFFT_Convolution.h:125): when a one-pass merged kernel exists for that axis
 	// the two sub-applications omit it
-	if (in.FFTdim >= 2 && nk == 1 && !in.crossPowerSpectrumNormalization && !in.frequencyZeroPadding && !in.isInputFormatted && !getenv("VKFFT_MI355X_CONV_SEPARATE")) {
+	if (in.FFTdim >= 2 && nk == 1 && !in.crossPowerSpectrumNormalization && !in.frequencyZeroPadding && !in.isInputFormatted && !sw.convSeparate) {
 		TransformDesc d;
 		d.fftDim = (int)in.FFTdim;
 		for (int i = 0; i < 4; i++) d.size[i] = in.size[i] ? in.size[i] : 1;
@@ -546,7 +539,8 @@ VkFFTResult initialize_convolution(VkFFTApplication* app, const VkFFTConfigurati
 			for (int i = 0; i < 4; i++) { d.bufStride[i] = in.bufferStride[i] ? in.bufferStride[i] : run; if (i + 1 < (int)in.FFTdim) run = d.bufStride[i] * d.size[i + 1]; }
 		}
 		for (pfUINT i = 0; i < in.FFTdim && i < 4; i++) if (in.performZeropadding[i] && in.fft_zeropad_right[i] > in.fft_zeropad_left[i]) { d.padL[i] = in.fft_zeropad_left[i]; d.padR[i] = in.fft_zeropad_right[i]; }
-		if (const char* e = getenv("VKFFT_MI355X_GENERIC_ONLY")) d.disableFastKernels = atoi(e) != 0;
+		d.sw = sw;
+		d.disableFastKernels = sw.genericOnly;
 		if (in.sharedMemorySize && in.sharedMemorySize < 160 * 1024) d.disableFastKernels = true;
 		if (in.userTempBuffer && in.tempBufferSize) d.userTempBytes = in.tempBufferSize[0];
 		ConvAxisDesc cd;
@@ -564,7 +558,7 @@ VkFFTResult initialize_convolution(VkFFTApplication* app, const VkFFTConfigurati
 				st->convMid = pl;
 				st->convInvFullCfg = b;
 				f.omitDimension[in.FFTdim - 1] = 1; b.omitDimension[in.FFTdim - 1] = 1;
-				if (in.printMemoryLayout || getenv("VKFFT_MI355X_PRINT_PLAN")) fprintf(stderr, "[vkfft_mi355x] convolution: axis %d merged (forward, %ux%u kernel product, inverse in one pass of pow2_col_blue_kernel)\n", (int)in.FFTdim - 1, cd.matrix, cd.matrix);
+				if (in.printMemoryLayout || sw.printPlan) fprintf(stderr, "[vkfft_mi355x] convolution: axis %d merged (forward, %ux%u kernel product, inverse in one pass of pow2_col_blue_kernel)\n", (int)in.FFTdim - 1, cd.matrix, cd.matrix);
 			} else free_direction(pl);
 		} else { free(pl); delete dpl; }
 	}

@@ -4,6 +4,7 @@
 // ahead-of-time compiled kernels instead of generating source.
 #pragma once
 #include "common.h"
+#include "switches.h"
 #include <vector>
 #include <string>
 #include <cstddef>
@@ -39,6 +40,7 @@ struct PassPlan {
 	size_t fusedLutBOff = (size_t)-1, fusedCtrOff = (size_t)-1, fusedRowTabOff = (size_t)-1;
 	int fusedWgPerCu = 0; // 0: what the occupancy query reports
 	bool auxIsKernel = false; // merged convolution pass: aux2 is bound to the caller's kernel buffer at launch (LaunchBuffers::kernel)
+	bool fusedProfile = false; // development build: per-phase cycle sums of every launch (Switches::fusedProfile)
 	std::string label;
 };
 
@@ -78,15 +80,11 @@ struct TransformDesc {
 	int fixMaxRadixBluestein = 0;
 	uint64_t raderMultMin = 17, raderMultMax = 128;
 	uint64_t userTempBytes = 0;  // >0: temp supplied by the caller with this size
-	bool disableFastKernels = false;
+	bool disableFastKernels = false; // Switches::genericOnly, or an LDS cap below what the hand-specialised kernels need
 	// zero padding (performZeropadding / fft_zeropad_left / fft_zeropad_right / frequencyZeroPadding): range [padL, padR) of an axis, padR == 0: none
 	uint64_t padL[4] = {0, 0, 0, 0}, padR[4] = {0, 0, 0, 0};
 	bool padFrequency = false;
-	// fused Four-Step (kernel_pow2_fused.h); the numeric fields are tuning knobs, 0 = planner default
-	bool fused = true;
-	int fusedMode = 2;
-	uint64_t fusedChunkBytes = 0;
-	uint32_t fusedLag = 0, fusedRing = 0, fusedWgPerCu = 0, fusedQueues = 0, fusedMarginPct = 0;
+	Switches sw;                 // the environment's switches as initializeVkFFT found them (switches.h): fixed for the lifetime of the plan
 };
 
 // returns 0 or a VkFFTResult code
@@ -119,19 +117,20 @@ int execute_direction(const DirectionPlan& plan, const LaunchBuffers& bufs, cons
 int launch_pow2(const PassPlan& pp, const PassParams& prm, hipStream_t stream);
 int launch_pow2_blue(const PassPlan& pp, const PassParams& prm, hipStream_t stream);
 int launch_pow2_col_blue(const PassPlan& pp, const PassParams& prm, hipStream_t stream);
-bool pow2_row_lookup(uint32_t log2n, bool dp, int* variant, int bits[4], int* fpw, int* threads, bool padded = false); // padded: only kernels with zero-padding masks
-bool pow2_col_lookup(uint32_t log2n, bool dp, int* variant, int bits[4], int* tc, int* threads);
+// want: the registered shape asked for (Switches, 0 = what ships; an index the size does not have = 0)
+bool pow2_row_lookup(uint32_t log2n, bool dp, int want, int* variant, int bits[4], int* fpw, int* threads, bool padded = false); // padded: only kernels with zero-padding masks
+bool pow2_col_lookup(uint32_t log2n, bool dp, int want, int* variant, int bits[4], int* tc, int* threads);
 bool pow2_col_blue_lookup(uint32_t log2l, bool dp, int mode, int* variant, int bits[4], int* tc, int* threads); // multi-pass Bluestein passes 1..3
 bool pow2_blue_r2r_lookup(uint32_t log2m, bool dp, uint32_t pre, int* variant, int bits[4], int* fpw, int* threads); // Bluestein-wrapped DCT/DST/R2C
 int launch_pow2_blue_r2r(const PassPlan& pp, const PassParams& prm, hipStream_t stream);
-bool pow2_blue_lookup(uint32_t log2m, bool dp, int* variant, int bits[4], int* fpw, int* threads); // fused Bluestein on padded length 2^log2m
+bool pow2_blue_lookup(uint32_t log2m, bool dp, int want, int* variant, int bits[4], int* fpw, int* threads); // fused Bluestein on padded length 2^log2m
 // fused Four-Step of 2^log2n = 2^la * 2^lb (kernels_fused.hip)
-bool pow2_fused_lookup(uint32_t log2n, bool dp, int mode, int* variant, int* la, int* lb, int bitsA[4], int bitsB[4], int* tca, int* tcb, int* threads, int* wgPerCu);
+bool pow2_fused_lookup(uint32_t log2n, bool dp, int mode, int want, int* variant, int* la, int* lb, int bitsA[4], int bitsB[4], int* tca, int* tcb, int* threads, int* wgPerCu);
 int launch_pow2_fused(const PassPlan& pp, const FusedParams& prm, hipStream_t stream);
 // the __global__ function behind a registry entry (vkfftMI355XDescribePlan: bench labels, rocprofv3 kernel names)
 const char* pow2_fused_kernel_name(int variant);
 // fused Four-Step of a non-power-of-two N = n0 * n1 (kernels_mixfused.hip, kernel_mix_fused.h)
-bool mix_fused_lookup(uint64_t n, bool dp, int* variant, int* n0, int* n1, int radA[5], int radB[5], int* tca, int* tcb, int* threads, int* wgPerCu);
+bool mix_fused_lookup(uint64_t n, bool dp, int want, int* variant, int* n0, int* n1, int radA[5], int radB[5], int* tca, int* tcb, int* threads, int* wgPerCu);
 int launch_mix_fused(const PassPlan& pp, const FusedParams& prm, hipStream_t stream);
 const char* pow2_row_kernel_name(int variant);
 bool mixed_row_lookup(uint64_t n, bool dp, int* variant, int rad[5], int* fpw, int* threads);

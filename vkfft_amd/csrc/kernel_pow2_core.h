@@ -25,6 +25,7 @@
 #include "butterflies.h"
 #include "memops.h"
 #include <cstdlib>
+#include <atomic>
 
 namespace vkfft_mi355x {
 
@@ -150,6 +151,42 @@ inline unsigned pow2_num_cus() { // CUs of the CURRENT device (plans are made an
 	if (!cache[dev]) cache[dev] = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? (unsigned)v : 256u;
 	return cache[dev];
 #endif
+}
+
+// persistent grid of a fused Four-Step launch (kernels_fused.hip, kernels_mixfused.hip): what the chip holds at once, at most one workgroup per ticket (the ticket
+// queue needs no co-residency: any grid is correct).  occ: the caller's cache of the occupancy query per device and variant; racing first calls compute the same
+// value, so a relaxed atomic is enough.  forcedWgPerCu: PassPlan::fusedWgPerCu
+constexpr int kFusedMaxDev = 32;
+template <int NV> uint64_t fused_grid(std::atomic<int> (&occ)[kFusedMaxDev][NV], int variant, const void* fn, int threads, int wgPerCu, int forcedWgPerCu, uint64_t tickets) {
+	int dev = 0, n = 0;
+#if !defined(VKFFT_HOSTEMU)
+	if (hipGetDevice(&dev) != hipSuccess || dev < 0) dev = 0;
+#endif
+	const bool cached = dev < kFusedMaxDev;
+	if (cached) n = occ[dev][variant].load(std::memory_order_relaxed);
+	if (!n) {
+#if defined(VKFFT_HOSTEMU)
+		n = 1;
+#else
+		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, threads, 0) != hipSuccess || n < 1) n = 1;
+#endif
+		if (cached) occ[dev][variant].store(n, std::memory_order_relaxed);
+	}
+	const uint64_t grid = (uint64_t)pow2_num_cus() * (forcedWgPerCu > 0 ? (uint32_t)forcedWgPerCu : (uint32_t)(n < wgPerCu ? n : wgPerCu));
+	return grid < tickets ? grid : tickets;
+}
+
+// registry look-ups: index of the want-th entry that match(i) accepts, else of the first one; -1: none.  match returns 0 (not this entry), 1 (yes) or 2 (an entry
+// of the size that this request cannot use: counted, not offered)
+template <typename F> int pick_variant(int count, int want, F match) {
+	int seen = 0, found = -1;
+	for (int i = 0; i < count; i++) {
+		const int m = match(i);
+		if (m == 0) continue;
+		if (m == 1) { if (found < 0) found = i; if (seen == want) return i; }
+		seen++;
+	}
+	return found;
 }
 
 struct Pow2Variant {

@@ -111,19 +111,8 @@ static const Pow2FusedVariant kPow2FusedVariants[] = {
 };
 constexpr int kNumPow2FusedVariants = (int)(sizeof(kPow2FusedVariants) / sizeof(kPow2FusedVariants[0]));
 
-bool pow2_fused_lookup(uint32_t log2n, bool dp, int mode, int* variant, int* la, int* lb, int bitsA[4], int bitsB[4], int* tca, int* tcb, int* threads, int* wgPerCu) {
-	int want = 0;
-	char name[64];
-	snprintf(name, sizeof(name), "VKFFT_MI355X_FUV%u", log2n);
-	if (const char* e = getenv(name)) want = atoi(e);
-	int seen = 0, found = -1;
-	for (int i = 0; i < kNumPow2FusedVariants; i++) {
-		const Pow2FusedVariant& v = kPow2FusedVariants[i];
-		if (v.log2n != (int)log2n || v.dp != dp || v.mode != mode) continue;
-		if (found < 0) found = i;
-		if (seen == want) { found = i; break; }
-		seen++;
-	}
+bool pow2_fused_lookup(uint32_t log2n, bool dp, int mode, int want, int* variant, int* la, int* lb, int bitsA[4], int bitsB[4], int* tca, int* tcb, int* threads, int* wgPerCu) {
+	const int found = pick_variant(kNumPow2FusedVariants, want, [&](int i) { const Pow2FusedVariant& v = kPow2FusedVariants[i]; return v.log2n == (int)log2n && v.dp == dp && v.mode == mode ? 1 : 0; });
 	if (found < 0) return false;
 	const Pow2FusedVariant& v = kPow2FusedVariants[found];
 	*variant = found; *la = v.la; *lb = v.lb; *tca = v.tca; *tcb = v.tcb; *threads = v.threads; *wgPerCu = v.wgPerCu;
@@ -139,30 +128,11 @@ const char* pow2_fused_kernel_name(int variant) {
 int launch_pow2_fused(const PassPlan& pp, const FusedParams& prm, hipStream_t stream) {
 	if (pp.variant < 0 || pp.variant >= kNumPow2FusedVariants) return 4039;
 	const Pow2FusedVariant& v = kPow2FusedVariants[pp.variant];
-	// persistent grid: what the chip holds at once (the ticket queue needs no co-residency: any grid is correct)
-	// (cached per device and variant; racing first calls compute the same value, so a relaxed atomic is enough)
-	constexpr int kMaxDev = 32;
-	static std::atomic<int> occ[kMaxDev][kNumPow2FusedVariants];
-	int dev = 0, n = 0;
-#if !defined(VKFFT_HOSTEMU)
-	if (hipGetDevice(&dev) != hipSuccess || dev < 0) dev = 0;
-#endif
-	const bool cached = dev < kMaxDev;
-	if (cached) n = occ[dev][pp.variant].load(std::memory_order_relaxed);
-	if (!n) {
-#if defined(VKFFT_HOSTEMU)
-		n = 1;
-#else
-		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, v.fn, v.threads, 0) != hipSuccess || n < 1) n = 1;
-#endif
-		if (cached) occ[dev][pp.variant].store(n, std::memory_order_relaxed);
-	}
-	const uint64_t tickets = (uint64_t)(prm.C + prm.D * prm.Q) << (prm.logG + prm.logTiles);
-	uint64_t grid = (uint64_t)pow2_num_cus() * (pp.fusedWgPerCu > 0 ? (uint32_t)pp.fusedWgPerCu : (uint32_t)std::min(n, v.wgPerCu));
-	if (grid > tickets) grid = tickets;
+	static std::atomic<int> occ[kFusedMaxDev][kNumPow2FusedVariants];
+	uint64_t grid = fused_grid(occ, pp.variant, v.fn, v.threads, v.wgPerCu, pp.fusedWgPerCu, (uint64_t)(prm.C + prm.D * prm.Q) << (prm.logG + prm.logTiles));
 	if (grid == 0) return 0;
 #if !defined(VKFFT_HOSTEMU)
-	if ((v.mode & 4) && getenv("VKFFT_MI355X_FUSED_PROFILE")) { // development: per-phase cycle sums (blocking)
+	if ((v.mode & 4) && pp.fusedProfile) { // development: per-phase cycle sums (blocking)
 		static unsigned long long* dbuf = nullptr;
 		if (!dbuf) (void)hipMalloc(&dbuf, 8192 * 24 * sizeof(unsigned long long));
 		FusedParams q = prm; q.prof = dbuf;

@@ -63,10 +63,8 @@ static const MixFusedVariant kMixFusedVariants[] = {
 constexpr uint64_t kMixFusedBlueQuery = 1ull << 63;
 constexpr int kNumMixFusedVariants = (int)(sizeof(kMixFusedVariants) / sizeof(kMixFusedVariants[0]));
 
-bool mix_fused_lookup(uint64_t n, bool dp, int* variant, int* n0, int* n1, int radA[5], int radB[5], int* tca, int* tcb, int* threads, int* wgPerCu) {
-	int want = 0;
-	if (const char* e = getenv("VKFFT_MI355X_MXFV")) want = atoi(e);
-	int seen = 0, found = -1;
+bool mix_fused_lookup(uint64_t n, bool dp, int want, int* variant, int* n0, int* n1, int radA[5], int radB[5], int* tca, int* tcb, int* threads, int* wgPerCu) {
+	int found = -1;
 	if (n & kMixFusedBlueQuery) {
 		const uint64_t minLen = n & ~kMixFusedBlueQuery;
 		for (int i = 0; i < kNumMixFusedVariants; i++) {
@@ -74,14 +72,7 @@ bool mix_fused_lookup(uint64_t n, bool dp, int* variant, int* n0, int* n1, int r
 			if (!v.blue || v.dp != dp || v.n < minLen) continue;
 			if (found < 0 || v.n < kMixFusedVariants[found].n) found = i;
 		}
-	} else
-	for (int i = 0; i < kNumMixFusedVariants; i++) {
-		const MixFusedVariant& v = kMixFusedVariants[i];
-		if (v.n != n || v.dp != dp || v.blue) continue;
-		if (found < 0) found = i;
-		if (seen == want) { found = i; break; }
-		seen++;
-	}
+	} else found = pick_variant(kNumMixFusedVariants, want, [&](int i) { const MixFusedVariant& v = kMixFusedVariants[i]; return v.n == n && v.dp == dp && !v.blue ? 1 : 0; });
 	if (found < 0) return false;
 	const MixFusedVariant& v = kMixFusedVariants[found];
 	*variant = found; *n0 = v.n0; *n1 = v.n1; *tca = v.tca; *tcb = v.tcb; *threads = v.threads; *wgPerCu = v.wgPerCu;
@@ -92,26 +83,8 @@ bool mix_fused_lookup(uint64_t n, bool dp, int* variant, int* n0, int* n1, int r
 int launch_mix_fused(const PassPlan& pp, const FusedParams& prm, hipStream_t stream) {
 	if (pp.variant < 0 || pp.variant >= kNumMixFusedVariants) return 4039;
 	const MixFusedVariant& v = kMixFusedVariants[pp.variant];
-	// persistent grid: what the chip holds at once (the ticket queue needs no co-residency: any grid is correct)
-	constexpr int kMaxDev = 32;
-	static std::atomic<int> occ[kMaxDev][kNumMixFusedVariants];
-	int dev = 0, n = 0;
-#if !defined(VKFFT_HOSTEMU)
-	if (hipGetDevice(&dev) != hipSuccess || dev < 0) dev = 0;
-#endif
-	const bool cached = dev < kMaxDev;
-	if (cached) n = occ[dev][pp.variant].load(std::memory_order_relaxed);
-	if (!n) {
-#if defined(VKFFT_HOSTEMU)
-		n = 1;
-#else
-		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, v.fn, v.threads, 0) != hipSuccess || n < 1) n = 1;
-#endif
-		if (cached) occ[dev][pp.variant].store(n, std::memory_order_relaxed);
-	}
-	const uint64_t tickets = (uint64_t)(prm.C + prm.D * prm.Q) * prm.tpc;
-	uint64_t grid = (uint64_t)pow2_num_cus() * (pp.fusedWgPerCu > 0 ? (uint32_t)pp.fusedWgPerCu : (uint32_t)std::min(n, v.wgPerCu));
-	if (grid > tickets) grid = tickets;
+	static std::atomic<int> occ[kFusedMaxDev][kNumMixFusedVariants];
+	const uint64_t grid = fused_grid(occ, pp.variant, v.fn, v.threads, v.wgPerCu, pp.fusedWgPerCu, (uint64_t)(prm.C + prm.D * prm.Q) * prm.tpc);
 	if (grid == 0) return 0;
 	MixFusedOps ops = {};
 	if (v.blue) { // chirp-z hooks: the planner left them in the pass descriptor's unused fields (emit_mix_fused_blue); the arena is where the stage twiddles are

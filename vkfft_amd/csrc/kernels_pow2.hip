@@ -108,7 +108,7 @@ static const Pow2Variant kPow2ColVariants[] = {
 };
 constexpr int kNumPow2ColVariants = (int)(sizeof(kPow2ColVariants) / sizeof(kPow2ColVariants[0]));
 
-// fused Bluestein on a power-of-two padded length: one entry per (log2 M, dp)
+// fused Bluestein on a power-of-two padded length: one entry per (log2 M, dp) (VKFFT_MI355X_P2B<log2 M>=k would select the k-th of several)
 template <typename T, typename SCH, int FPW> void pow2_blue_launch(const PassParams& prm, dim3 grid, hipStream_t s) {
 	constexpr int threads = ((1 << SCH::LOGN) >> SCH::LOGE) * FPW;
 	const unsigned resident = pow2_num_cus() * 8u; // persistent: the workgroups stride over the row tiles
@@ -195,30 +195,19 @@ int launch_pow2(const PassPlan& pp, const PassParams& prm, hipStream_t stream) {
 }
 
 
-static bool pow2_lookup(const Pow2Variant* tab, int ntab, const char* envPrefix, uint32_t log2n, bool dp, int* variant, int bits[4], int* fpw, int* threads, bool padded = false) {
-	int want = 0;
-	char name[64];
-	snprintf(name, sizeof(name), "%s%u", envPrefix, log2n);
-	if (const char* e = getenv(name)) want = atoi(e);
-	int seen = 0, found = -1;
-	for (int i = 0; i < ntab; i++) {
-		if (tab[i].log2n != (int)log2n || tab[i].dp != dp) continue;
-		if (padded && tab[i].noPadMasks) { seen++; continue; }
-		if (found < 0) found = i;
-		if (seen == want) { found = i; break; }
-		seen++;
-	}
+static bool pow2_lookup(const Pow2Variant* tab, int ntab, int want, uint32_t log2n, bool dp, int* variant, int bits[4], int* fpw, int* threads, bool padded = false) {
+	const int found = pick_variant(ntab, want, [&](int i) { return tab[i].log2n != (int)log2n || tab[i].dp != dp ? 0 : padded && tab[i].noPadMasks ? 2 : 1; });
 	if (found < 0) return false;
 	*variant = found;
 	for (int k = 0; k < 4; k++) bits[k] = tab[found].bits[k];
 	*fpw = tab[found].fpw; *threads = tab[found].threads;
 	return true;
 }
-bool pow2_row_lookup(uint32_t log2n, bool dp, int* variant, int bits[4], int* fpw, int* threads, bool padded) {
-	return pow2_lookup(kPow2Variants, kNumPow2Variants, "VKFFT_MI355X_P2V", log2n, dp, variant, bits, fpw, threads, padded);
+bool pow2_row_lookup(uint32_t log2n, bool dp, int want, int* variant, int bits[4], int* fpw, int* threads, bool padded) {
+	return pow2_lookup(kPow2Variants, kNumPow2Variants, want, log2n, dp, variant, bits, fpw, threads, padded);
 }
-bool pow2_col_lookup(uint32_t log2n, bool dp, int* variant, int bits[4], int* tc, int* threads) {
-	return pow2_lookup(kPow2ColVariants, kNumPow2ColVariants, "VKFFT_MI355X_P2C", log2n, dp, variant, bits, tc, threads);
+bool pow2_col_lookup(uint32_t log2n, bool dp, int want, int* variant, int bits[4], int* tc, int* threads) {
+	return pow2_lookup(kPow2ColVariants, kNumPow2ColVariants, want, log2n, dp, variant, bits, tc, threads);
 }
 
 bool pow2_col_blue_lookup(uint32_t log2l, bool dp, int mode, int* variant, int bits[4], int* tc, int* threads) {
@@ -232,8 +221,8 @@ bool pow2_col_blue_lookup(uint32_t log2l, bool dp, int mode, int* variant, int b
 	}
 	return false;
 }
-bool pow2_blue_lookup(uint32_t log2m, bool dp, int* variant, int bits[4], int* fpw, int* threads) {
-	return pow2_lookup(kPow2BlueVariants, kNumPow2BlueVariants, "VKFFT_MI355X_P2B", log2m, dp, variant, bits, fpw, threads);
+bool pow2_blue_lookup(uint32_t log2m, bool dp, int want, int* variant, int bits[4], int* fpw, int* threads) {
+	return pow2_lookup(kPow2BlueVariants, kNumPow2BlueVariants, want, log2m, dp, variant, bits, fpw, threads);
 }
 
 

@@ -100,7 +100,12 @@ static uint32_t ceil_log2(uint64_t v) { uint32_t l = 0; while ((1ull << l) < v) 
 
 static void host_fft(std::vector<cld>& a);
 
+// buffer addressing of the fast kernels (32-bit offsets from a tile's base): a tile must span less than 2 GiB on both sides
+constexpr uint64_t kSpanLimit = 0x7FFFFF00ull;
+
 struct PassBuild {
+	const Switches& sw; // the plan's snapshot of the environment (TransformDesc::sw)
+	explicit PassBuild(const Switches& s) : sw(s) {}
 	uint64_t L = 0;
 	int64_t inStrideJ = 1, outStrideJ = 1;
 	std::vector<HostDim> dims; // dims[0] tiled
@@ -187,9 +192,9 @@ static void make_mixrad_tables(uint64_t P, uint64_t M, bool dp, Arena& ar, size_
 // A row of L = M * P complex points on the Rader-stage kernel (kernel_mixrad.h): P the largest prime factor (37 or more, with a Rader row instance), M a cofactor
 // that splits into the kernel's column radices (mixrad_plan.h).  VKFFT_MI355X_MIXRAD=0: off; VKFFT_MI355X_MIXRAD_LDS_KIB: the LDS budget of a tile (tuning)
 struct MixradChoice { uint64_t P = 0, M = 0, len = 0; uint32_t A = 0, rows = 0, aligned = 0; int variant = -1, rad[5] = {1, 1, 1, 1, 1}, fpw = 0, threads = 0; double cost = 2.0; };
-static bool mixrad_choose(uint64_t L, bool dp, bool ops, MixradChoice& c) { // ops: a real transform between the table-driven maps
+static bool mixrad_choose(const Switches& sw, uint64_t L, bool dp, bool ops, MixradChoice& c) { // ops: a real transform between the table-driven maps
 	if (dp || L < 37 || L > kMixradLongest) return false;
-	if (getenv("VKFFT_MI355X_MIXRAD") && atoi(getenv("VKFFT_MI355X_MIXRAD")) == 0) return false;
+	if (sw.mixrad == 0) return false;
 	uint64_t P = 0, rest = L;
 	for (uint64_t q = 2; q * q <= rest; q++) while (rest % q == 0) { P = q; rest /= q; }
 	if (rest > 1) P = rest; // largest prime factor
@@ -197,21 +202,21 @@ static bool mixrad_choose(uint64_t L, bool dp, bool ops, MixradChoice& c) { // o
 	const uint64_t M = L / P;
 	uint32_t A = 0, B = 1;
 	if (M == 1) { // a prime's own rows: no column step (VKFFT_MI355X_MIXRAD_PRIMES=1; default: kernel_mixconv.h)
-		if (!(getenv("VKFFT_MI355X_MIXRAD_PRIMES") && atoi(getenv("VKFFT_MI355X_MIXRAD_PRIMES")) == 1)) return false; // (off by default: measured slower than kernel_mixconv.h)
+		if (sw.mixradPrimes != 1) return false; // (off by default: measured slower than kernel_mixconv.h)
 		A = 1;
 	} else if (M == P) A = 0; // P * P: the column transform is the prime's own convolution (kernel_mixrad.h, 2b)
 	else if (!mixrad_split((uint32_t)M, A, B)) return false;
 	uint64_t len; int sp = 0, lutn = 0, groups = 0, gd = 0;
 	if (!mixconv_lookup(true, false, P, dp, &c.variant, &len, c.rad, &c.fpw, &c.threads) || !mixrad_geom(c.variant, &sp, &lutn, &groups, &gd)) return false;
 	if (gd <= 0 || sp <= 0) return false; // (an instance without the stage form — the registry leaves its geometry at zero: DST-I of 1782 reals, 2 * 1783 complex points, divided by it)
-	const uint64_t budget = (getenv("VKFFT_MI355X_MIXRAD_LDS_KIB") ? (uint64_t)atoll(getenv("VKFFT_MI355X_MIXRAD_LDS_KIB")) : 40ull) << 10;
+	const uint64_t budget = sw.mixradLdsBytes;
 	const bool twoSets = ops && mixrad_two_sets((uint32_t)M, A);
 	c.P = P; c.M = M; c.A = A; c.len = len;
 	// layout of the convolution's thread groups (kernel_mixrad.h MixradGeom): the wave-aligned one runs its rounds without workgroup barriers (a round costs about 0.8
 	// of a dense one: 3144, 3130, 3611, 314 1.2-1.5x faster) but may have fewer groups than the dense FPW — a round more where the cofactor was matched to FPW
 	// (3232 = 32 * 101, 2032 = 16 * 127: 0.9x).  Cost of a row = rounds per tile / rows per tile, per layout with its own tile
 	c.rows = mixrad_rows((uint32_t)P, (uint32_t)sp, (uint32_t)lutn, (uint32_t)gd, (uint32_t)M, dp ? 16u : 8u, budget, twoSets);
-	if (groups > 0 && !getenv("VKFFT_MI355X_MIXRAD_DENSE")) {
+	if (groups > 0 && !sw.mixradDense) {
 		const uint32_t ra = mixrad_rows((uint32_t)P, (uint32_t)sp, (uint32_t)lutn, (uint32_t)groups, (uint32_t)M, dp ? 16u : 8u, budget, twoSets);
 		auto cost = [&](uint32_t rows, uint32_t g, double w) { const uint64_t jobs = (uint64_t)rows * M; return w * (double)((jobs + g - 1) / g) / (double)rows; };
 		if (cost(ra, (uint32_t)groups, 0.8) <= cost(c.rows, (uint32_t)gd, 1.0)) { c.rows = ra; c.aligned = 1; }
@@ -228,10 +233,9 @@ static bool mixrad_choose(uint64_t L, bool dp, bool ops, MixradChoice& c) { // o
 
 // Real-transform families that can carry TWO rows per complex transform (kernel_generic.h ops_rows_in / ops_rows_out): the pre-map of a row is a real
 // sequence (R2C of odd length, DCT / DST-I, -II and odd -IV in their full-length forms) or the result is real (C2R of odd length, DCT / DST-III).
-// 0: never over a fused-map instance; 1: every pairable family; 2 (default since round 6): DCT-II / -III and the odd DCT-IV — measured with the planner forced either way on every
+// VKFFT_MI355X_PAIR_PREFER = 0: never over a fused-map instance; 1: every pairable family; 2 (default since round 6): DCT-II / -III and the odd DCT-IV — measured with the planner forced either way on every
 // length 4 ... 400 (profiles/r06_real_rows_pairs_preferred_over_fused_map_instances.jsonl): DCT-IV of 5, 25, 35 ... 245 reals 1.10-1.83x faster between the tables than on
 // their fused-map instance (none slower), DCT-II / -III of 7, 25, 49, 175, 343 1.03-1.45x; R2C / C2R mixed (7: 1.29x, 25 and 49: 0.75x) and left where they were
-constexpr int kPairPreferDefault = 2;
 static bool pairable_family(uint32_t pre, uint32_t post, uint64_t cplxLen, uint32_t opN) {
 	auto fam = [&](uint32_t a, uint32_t c) { return pre == a && post == c; };
 	const bool odd4 = (fam(OP_DCT4_PRE, OP_DCT4_POST) || fam(OP_DST4_PRE, OP_DST4_POST)) && cplxLen == opN;
@@ -264,9 +268,6 @@ static TmFamily tm_family(uint32_t pre, uint32_t post, uint64_t Lc, uint32_t N) 
 	}
 	return TM_NONE;
 }
-// threads per row from which the table-driven maps replace the generic ones: 1 — since the staging tile of round 5 (rows with fewer than eight threads move as one
-// contiguous run through LDS, kernel_mixed.h) the tables win at every shape measured (31 reals, one thread per row: 0.45 -> 0.19 ms); the switch stays for A/B runs
-static int tmaps_min_tpf() { return getenv("VKFFT_MI355X_TMAPS_MIN_TPF") ? atoi(getenv("VKFFT_MI355X_TMAPS_MIN_TPF")) : 1; }
 static bool tm_family_pairs(TmFamily f) { return f != TM_NONE && f != TM_R2R4_EVEN; }
 struct TmTable {
 	Arena& ar; size_t off; uint32_t n; bool dp;
@@ -406,14 +407,12 @@ static int finish_pass(const PassBuild& bIn, Arena& ar, PassPlan& pp) {
 	if (b.allowFast && b.fastKernel == KERNEL_GENERIC && b.colIn && b.L >= 2 && b.L <= 1024 && (b.L & (b.L - 1)) == 0 && b.preOp == OP_NONE
 	    && b.midOp == OP_NONE && (b.postOp == OP_NONE || b.postOp == OP_TWIDDLE_4STEP) && !b.realIn && !b.realOut && !b.forceT) {
 		int variant, bits[4], tc, thr;
-		// buffer addressing of the fast kernels: a tile must span less than 2 GiB on both sides
 		const uint64_t esz = b.dp ? 16 : 8;
 		const HostDim d0 = b.dims.empty() ? HostDim{1, 0, 0} : b.dims[0];
 		const uint64_t spanIn = (b.L * (uint64_t)std::llabs(b.inStrideJ) + 64 * (uint64_t)std::llabs(d0.inStride)) * esz;
 		const uint64_t spanOut = (b.L * (uint64_t)std::llabs(b.outStrideJ) + 64 * (uint64_t)std::llabs(d0.outStride)) * esz;
-		if (pow2_col_lookup(ilog2(b.L), b.dp, &variant, bits, &tc, &thr)) {
-			static const bool forceBig = getenv("VKFFT_MI355X_FORCE_BIGSPAN") != nullptr; // (tests: the 64-bit form on small problems)
-			b.bigSpan = forceBig || !(spanIn < 0x7FFFFF00ull && spanOut < 0x7FFFFF00ull); // (then the kernel's 64-bit form: DESIGN 7, the z axis of 1024^3 on one GPU)
+		if (pow2_col_lookup(ilog2(b.L), b.dp, Switches::shape(b.sw.pow2ColShape, ilog2(b.L)), &variant, bits, &tc, &thr)) {
+			b.bigSpan = b.sw.forceBigSpan || !(spanIn < kSpanLimit && spanOut < kSpanLimit); // (then the kernel's 64-bit form: DESIGN 7, the z axis of 1024^3 on one GPU)
 			b.fastKernel = KERNEL_POW2_COL; b.fastVariant = variant; b.fastThreads = thr; b.forceT = (uint32_t)tc;
 			b.radices.clear();
 			for (int k = 0; k < 4; k++) if (bits[k]) b.radices.push_back(1u << bits[k]);
@@ -426,7 +425,7 @@ static int finish_pass(const PassBuild& bIn, Arena& ar, PassPlan& pp) {
 		int variant, bits[4], fpw, thr;
 		const HostDim d0 = b.dims.empty() ? HostDim{1, 0, 0} : b.dims[0];
 		const uint64_t span = (b.L + 64 * (uint64_t)std::max<int64_t>(std::llabs(d0.inStride), std::llabs(d0.outStride))) * (b.dp ? 16 : 8);
-		if (span < 0x7FFFFF00ull && b.opN * 2 <= b.L && pow2_blue_lookup(ilog2(b.L), b.dp, &variant, bits, &fpw, &thr)) {
+		if (span < kSpanLimit && b.opN * 2 <= b.L && pow2_blue_lookup(ilog2(b.L), b.dp, Switches::shape(b.sw.pow2BlueShape, ilog2(b.L)), &variant, bits, &fpw, &thr)) {
 			b.fastKernel = KERNEL_POW2_BLUE; b.fastVariant = variant; b.fastThreads = thr; b.forceT = (uint32_t)fpw;
 			b.radices.clear();
 			for (int k = 0; k < 4; k++) if (bits[k]) b.radices.push_back(1u << bits[k]);
@@ -440,7 +439,7 @@ static int finish_pass(const PassBuild& bIn, Arena& ar, PassPlan& pp) {
 		const HostDim d0 = b.dims.empty() ? HostDim{1, 0, 0} : b.dims[0];
 		const uint64_t spanIn = (b.L * (uint64_t)std::llabs(b.inStrideJ) + 64 * (uint64_t)std::llabs(d0.inStride)) * esz;
 		const uint64_t spanOut = (b.L * (uint64_t)std::llabs(b.outStrideJ) + 64 * (uint64_t)std::llabs(d0.outStride)) * esz;
-		if (spanIn < 0x7FFFFF00ull && spanOut < 0x7FFFFF00ull && b.opN * 2 <= b.L && pow2_col_blue_lookup(ilog2(b.L), b.dp, 5, &variant, bits, &tc, &thr)) {
+		if (spanIn < kSpanLimit && spanOut < kSpanLimit && b.opN * 2 <= b.L && pow2_col_blue_lookup(ilog2(b.L), b.dp, 5, &variant, bits, &tc, &thr)) {
 			b.fastKernel = KERNEL_POW2_COL_BLUE; b.fastVariant = variant; b.fastThreads = thr; b.forceT = (uint32_t)tc;
 			b.radices.clear();
 			for (int k = 0; k < 4; k++) if (bits[k]) b.radices.push_back(1u << bits[k]);
@@ -458,7 +457,7 @@ static int finish_pass(const PassBuild& bIn, Arena& ar, PassPlan& pp) {
 	{
 		// measured (tools/tune_mixed_ops.py, profiles/r03_short_real_rows_fused_maps_vs_instance_between_maps.jsonl): complex lengths 8 and 16 (R2C / DCT of 16 and
 		// 32 reals) run 1.1-5x faster between the maps; from 20 on the fused-map kernels win (only the powers of two were measured: the others keep their fused-map kernel)
-		const uint64_t lim = getenv("VKFFT_MI355X_MIXED_OPS_MAX") ? (uint64_t)atoll(getenv("VKFFT_MI355X_MIXED_OPS_MAX")) : 16;
+		const uint64_t lim = b.sw.mixedOpsMax;
 		int v, r5[5], f, t;
 		// (round 4: the other lengths of that range too — their fused-map instances are one thread per row, radix-10 / 14 / 15 butterflies fed by loads a row pitch
 		// apart per lane: DCT-IV of 20 and 30 reals ran at 0.19 / 0.14x the reference, DCT-II of 28 at 0.22x, profiles/r04_dct4_rows_5_400_*)
@@ -466,7 +465,7 @@ static int finish_pass(const PassBuild& bIn, Arena& ar, PassPlan& pp) {
 		preferMixedOps = lim && b.L >= 8 && b.L <= lim && rowOp && mixed_row_lookup(b.L, b.dp, &v, r5, &f, &t);
 		// two real rows per transform exist only between the generic maps (PassParams::pairRows): VKFFT_MI355X_PAIR_PREFER=1 sends the pairable families there
 		// even where a fused-map instance exists (measurement switch)
-		const int pairPrefer = getenv("VKFFT_MI355X_PAIR_PREFER") ? atoi(getenv("VKFFT_MI355X_PAIR_PREFER")) : kPairPreferDefault;
+		const int pairPrefer = b.sw.pairPrefer;
 		const bool r2cFam = b.preOp == OP_R2C_FULL || b.preOp == OP_C2R_FULL || b.postOp == OP_R2C_FULL || b.postOp == OP_C2R_FULL;
 		if (!preferMixedOps && (pairPrefer == 1 || (pairPrefer == 2 && !r2cFam)) && rowOp && pairable_family(b.preOp, b.postOp, b.L, b.opN) && mixed_row_lookup(b.L, b.dp, &v, r5, &f, &t)) preferMixedOps = true;
 	}
@@ -478,7 +477,7 @@ static int finish_pass(const PassBuild& bIn, Arena& ar, PassPlan& pp) {
 		const uint64_t spanIn = (maxPos * (uint64_t)std::llabs(b.inStrideJ) + 64 * (uint64_t)std::llabs(d0.inStride)) * ib;
 		const uint64_t spanOut = (maxPos * (uint64_t)std::llabs(b.outStrideJ) + 64 * (uint64_t)std::llabs(d0.outStride)) * ob;
 		int variant, rad5[5], fpw, thr;
-		if (spanIn < 0x7FFFFF00ull && spanOut < 0x7FFFFF00ull && opfft_lookup(b.L, b.dp, b.colIn, transOut, b.preOp, b.postOp, &variant, rad5, &fpw, &thr)) {
+		if (spanIn < kSpanLimit && spanOut < kSpanLimit && opfft_lookup(b.L, b.dp, b.colIn, transOut, b.preOp, b.postOp, &variant, rad5, &fpw, &thr)) {
 			b.fastKernel = KERNEL_OPFFT; b.fastVariant = variant; b.fastThreads = thr; b.forceT = (uint32_t)fpw;
 			for (int k = 0; k < 5; k++) if (rad5[k] > 1) b.radices.push_back((uint32_t)rad5[k]);
 		}
@@ -491,25 +490,25 @@ static int finish_pass(const PassBuild& bIn, Arena& ar, PassPlan& pp) {
 		};
 		if (b.allowOp && b.fastKernel == KERNEL_GENERIC && !b.forceT && b.midOp == OP_NONE && !b.colIn && !b.colOut && b.radices.empty() && !b.preNat && !b.postNat &&
 		    b.auxOff2ForPre == (size_t)-1 && (b.preOp != OP_NONE || b.postOp != OP_NONE) && realOp(b.preOp) && realOp(b.postOp) && b.inStrideJ == 1 && b.outStrideJ == 1 &&
-		    !getenv("VKFFT_MI355X_NO_MIXED_OPS")) {
+		    !b.sw.noMixedOps) {
 			int variant, rad5[5], fpw, thr;
 			uint64_t len = 0;
 			opsCplxLen = b.L;
 			// (the maps inside the stages address the rows of a tile — up to 2 * FPW <= 128 of them — with 32-bit byte offsets from the tile's base: a row pitch that
 			// takes the tile past 2 GiB leaves the pass to the interpreter, as on the complex paths)
 			const HostDim d0o = b.dims.empty() ? HostDim{1, 0, 0} : b.dims[0];
-			const bool spanOK = (2 * b.L + 128 * (uint64_t)std::max<int64_t>(std::llabs(d0o.inStride), std::llabs(d0o.outStride))) * (b.dp ? 16 : 8) < 0x7FFFFF00ull;
+			const bool spanOK = (2 * b.L + 128 * (uint64_t)std::max<int64_t>(std::llabs(d0o.inStride), std::llabs(d0o.outStride))) * (b.dp ? 16 : 8) < kSpanLimit;
 			if (!spanOK) { /* interpreter */ }
 			else if (mixed_row_lookup(b.L, b.dp, &variant, rad5, &fpw, &thr)) {
 				const int fo = mixed_row_ops_fpw(variant); // (the form between the maps may take fewer rows per workgroup: kernel_mixed.h mixed_ops_fpw)
 				if (fo > 0 && fo != fpw) { thr = thr / fpw * fo; fpw = fo; }
 				b.fastKernel = KERNEL_MIXED_ROW; b.fastVariant = variant; b.fastThreads = thr; b.forceT = (uint32_t)fpw;
 				for (int k = 0; k < 5; k++) if (rad5[k] > 1) b.radices.push_back((uint32_t)rad5[k]);
-			} else if (!padMask && tm_family(b.preOp, b.postOp, b.L, b.opN) != TM_NONE && !getenv("VKFFT_MI355X_NO_TMAPS") && [&]() {
+			} else if (!padMask && tm_family(b.preOp, b.postOp, b.L, b.opN) != TM_NONE && !b.sw.noTmaps && [&]() {
 				// the complex length is M * P with a Rader prime and a served cofactor: mixrad_kernel between the table-driven maps (kernel_mixrad.h, kernel_tmaps.h)
 				MixradChoice mr;
-				if (!mixrad_choose(b.L, b.dp, true, mr)) return false;
-				if ((2 * (uint64_t)mr.rows + 2) * (uint64_t)std::max<int64_t>(std::llabs(d0o.inStride), std::llabs(d0o.outStride)) * (b.dp ? 16 : 8) >= 0x7FFFFF00ull) return false;
+				if (!mixrad_choose(b.sw, b.L, b.dp, true, mr)) return false;
+				if ((2 * (uint64_t)mr.rows + 2) * (uint64_t)std::max<int64_t>(std::llabs(d0o.inStride), std::llabs(d0o.outStride)) * (b.dp ? 16 : 8) >= kSpanLimit) return false;
 				const uint64_t N = b.L;
 				if (!b.inLen) b.inLen = (uint32_t)N;
 				if (!b.outLen) b.outLen = (uint32_t)N;
@@ -691,17 +690,17 @@ static int finish_pass(const PassBuild& bIn, Arena& ar, PassPlan& pp) {
 	const uint64_t padded = p.padShift >= 31 ? b.L : b.L + (b.L >> p.padShift);
 	p.ldsElems = (uint32_t)((padded + 1) * p.Tp);
 	p.tilesPerG0 = (uint32_t)((dims[0].count + T - 1) / T);
-	const bool noPairs = getenv("VKFFT_MI355X_NO_ROW_PAIRS") != nullptr;
+	const bool noPairs = b.sw.noRowPairs;
 	if (opsCplxLen && b.fastKernel != KERNEL_GENERIC && (!noPairs || b.raderM)) { // (the Rader-stage kernel has no other maps than the tables: kernel_mixrad.h)
 		// two real rows per complex transform (the reference's mergeSequencesR2C, vkFFT_SharedMemory.h:40): the families whose pre-map is a real sequence
 		// (post-map through the even / odd split) or whose result is real (kernel_generic.h ops_rows_in / ops_rows_out); the tile holds 2 T rows
 		// table-driven maps (kernel_tmaps.h): the instance transform of kernel_mixed.h; with them the families whose operation the generic maps only know at run time pair too
-		const TmFamily tmf = ((((b.fastKernel == KERNEL_MIXED_ROW || (b.fastKernel == KERNEL_MIXCONV && !b.raderM)) && b.fastThreads / (int)T >= tmaps_min_tpf()) || (b.fastKernel == KERNEL_MIXCONV && b.raderM)) && !b.padInN && !b.padOutN && !getenv("VKFFT_MI355X_NO_TMAPS")) ? tm_family(b.preOp, b.postOp, opsCplxLen, b.opN) : TM_NONE;
+		const TmFamily tmf = ((((b.fastKernel == KERNEL_MIXED_ROW || (b.fastKernel == KERNEL_MIXCONV && !b.raderM)) && b.fastThreads / (int)T >= b.sw.tmapsMinTpf) || (b.fastKernel == KERNEL_MIXCONV && b.raderM)) && !b.padInN && !b.padOutN && !b.sw.noTmaps) ? tm_family(b.preOp, b.postOp, opsCplxLen, b.opN) : TM_NONE;
 		// (the one family that does not pair — even DCT / DST-IV on its half-length complex form — with fewer than four threads per row: the staged tile of ONE row per
 		// thread measured 1.8x slower than the generic loops: DCT-IV of 20 and 30 reals, profiles/r05_dct4_rows_reference_every_length_step3_*; and the maps address
 		// the 2 T real rows of a tile with 32-bit byte offsets from the tile's base)
 		const uint64_t tmReach = (2 * (uint64_t)T + 2) * (uint64_t)std::max<int64_t>(std::llabs(dims[0].inStride), std::llabs(dims[0].outStride)) * (dp ? 16 : 8);
-		const bool tmOn = tmf != TM_NONE && !(tmf == TM_R2R4_EVEN && !b.raderM && b.fastThreads / (int)T < 4) && tmReach < 0x7FFFFF00ull;
+		const bool tmOn = tmf != TM_NONE && !(tmf == TM_R2R4_EVEN && !b.raderM && b.fastThreads / (int)T < 4) && tmReach < kSpanLimit;
 		if (b.raderM && !tmOn) return 3002;
 		if (!noPairs && (pairable_family(b.preOp, b.postOp, opsCplxLen, b.opN) || (tmOn && tm_family_pairs(tmf)))) {
 			p.pairRows = 1;
@@ -712,7 +711,7 @@ static int finish_pass(const PassBuild& bIn, Arena& ar, PassPlan& pp) {
 			build_tmaps(tmf, dstFam, opsCplxLen, b.opN, dp, b.scale, b.fastKernel == KERNEL_MIXED_ROW && b.fastThreads / (int)T >= 8, ar, pp);
 		}
 	}
-	if (b.fastKernel == KERNEL_POW2_BLUE_R2R && !b.padInN && !b.padOutN && !getenv("VKFFT_MI355X_NO_ROW_PAIRS") && !getenv("VKFFT_MI355X_NO_BLUE_PAIRS")) {
+	if (b.fastKernel == KERNEL_POW2_BLUE_R2R && !b.padInN && !b.padOutN && !noPairs && !b.sw.noBluePairs) {
 		// two real rows per fused Bluestein transform (kernel_blue_r2r.h): the families whose embedding sequence is real, or whose result is
 		auto fam = [&](uint32_t a, uint32_t c) { return b.preOp == a && b.postOp == c; };
 		const bool same4 = (fam(OP_DCT4_PRE, OP_DCT4_POST) || fam(OP_DST4_PRE, OP_DST4_POST)) && b.blueN == b.opN;
@@ -731,7 +730,7 @@ static int finish_pass(const PassBuild& bIn, Arena& ar, PassPlan& pp) {
 		const uint64_t esz = dp ? 16 : 8;
 		const uint64_t reach = ((uint64_t)T / dims[0].count + 2) * (uint64_t)std::max<int64_t>(std::llabs(dims[1].inStride), std::llabs(dims[1].outStride))
 		                     + (b.L + 1) * (uint64_t)std::max<int64_t>(std::llabs(b.inStrideJ), std::llabs(b.outStrideJ)) + dims[0].count;
-		if (reach * esz < 0x7FFFFF00ull && dims[1].inStride > 0 && dims[1].outStride > 0) {
+		if (reach * esz < kSpanLimit && dims[1].inStride > 0 && dims[1].outStride > 0) {
 			p.colMerge = 1;
 			p.tilesPerG0 = (uint32_t)(((uint64_t)dims[0].count * dims[1].count + T - 1) / T);
 		}
@@ -802,7 +801,7 @@ static bool is_supported_len(uint64_t L, uint32_t directMax) {
 // middle pass with twiddle, last pass)
 static bool fast_col_len(uint64_t L, bool dp) {
 	int v, r5[5], bits[4], f, t;
-	if ((L & (L - 1)) == 0 && L >= 16 && L <= 1024) return pow2_col_lookup(ilog2(L), dp, &v, bits, &f, &t);
+	if ((L & (L - 1)) == 0 && L >= 16 && L <= 1024) return pow2_col_lookup(ilog2(L), dp, 0, &v, bits, &f, &t); // (whether the length is served: every shape index finds one)
 	return opfft_lookup(L, dp, true, true, OP_NONE, OP_TWIDDLE_4STEP, &v, r5, &f, &t) && opfft_lookup(L, dp, true, false, OP_NONE, OP_TWIDDLE_4STEP, &v, r5, &f, &t)
 	       && opfft_lookup(L, dp, true, false, OP_NONE, OP_NONE, &v, r5, &f, &t);
 }
@@ -1059,11 +1058,11 @@ static size_t build_pow2_stage_lut(Arena& ar, const int bits[4], bool dp) {
 // intermediate lives in a small scratch ring (Infinity-Cache resident) instead of a full-size temp buffer.  The other dimensions must
 // collapse into one batch progression on both sides.  Returns false when the plan does not qualify (the caller emits separate passes).
 static bool emit_fused(const TransformDesc& d, const AxisJob& j, Arena& ar, DirectionPlan& out, std::vector<PassPlan>& passes) {
-	if (!d.fused || d.disableFastKernels || (j.N & (j.N - 1)) != 0 || j.inStrideJ != 1 || j.outStrideJ != 1) return false;
+	if (!d.sw.fused || d.disableFastKernels || (j.N & (j.N - 1)) != 0 || j.inStrideJ != 1 || j.outStrideJ != 1) return false;
 	const bool dp = j.dp;
 	const uint64_t es = dp ? 16 : 8;
 	int variant, la, lb, bitsA[4], bitsB[4], tca, tcb, thr, wgPerCu;
-	if (!pow2_fused_lookup(ilog2(j.N), dp, d.fusedMode, &variant, &la, &lb, bitsA, bitsB, &tca, &tcb, &thr, &wgPerCu)) return false;
+	if (!pow2_fused_lookup(ilog2(j.N), dp, d.sw.fusedMode, Switches::shape(d.sw.pow2FusedShape, ilog2(j.N)), &variant, &la, &lb, bitsA, bitsB, &tca, &tcb, &thr, &wgPerCu)) return false;
 	// one batch progression
 	uint64_t batch = 1; int64_t inS = (int64_t)j.N, outS = (int64_t)j.N; bool first = true;
 	for (const HostDim& o : j.others) {
@@ -1079,7 +1078,7 @@ static bool emit_fused(const TransformDesc& d, const AxisJob& j, Arena& ar, Dire
 	// are handed out in order, so at any moment its Wq workgroups hold a window of about Wq consecutive tickets.  A wait is avoided
 	// when the producer tiles of a dependency left that window before the consumer enters it: lag D = 1 + X slots between a chunk's A
 	// and B tiles, ring NS = D + 1 + X slots before a slot is rewritten, X slots ~ margin * Wq tickets.
-	const uint64_t chunkTarget = d.fusedChunkBytes ? d.fusedChunkBytes : (1ull << 20);
+	const uint64_t chunkTarget = d.sw.fusedChunkBytes ? d.sw.fusedChunkBytes : (1ull << 20);
 	uint32_t logG = 0;
 	while ((fftBytes << (logG + 1)) <= chunkTarget && (1ull << (logG + 1)) <= batch) logG++;
 	const uint64_t G = 1ull << logG;
@@ -1090,29 +1089,29 @@ static bool emit_fused(const TransformDesc& d, const AxisJob& j, Arena& ar, Dire
 	// (2^22 fp32: a transform is 32 MiB, the budget decides between lag 3 / ring 6 and lag 4 / ring 8 — measured 2.73 against 3.04 TB/s with the tiles of two
 	// halves, profiles/r05_fused_lag_ring_pairs.jsonl: with lag 3 a tile waits 5-10 k cycles per ticket for the previous tenant of its ring slot)
 	const uint64_t ringBudget = fftBytes >= (32ull << 20) ? (256ull << 20) : (224ull << 20);
-	const uint64_t wgs = 256ull * (uint64_t)(d.fusedWgPerCu ? d.fusedWgPerCu : wgPerCu);
+	const uint64_t wgs = 256ull * (uint64_t)(d.sw.fusedWgPerCu ? d.sw.fusedWgPerCu : wgPerCu);
 	// measured (tools/tune_fused.py): completions are published up to a ticket late and the ticket rate rises with the speed of the
 	// kernel, so the window is taken generously: 3 windows where two or more workgroups share a CU, 2 with one workgroup per CU
 	// (round 4, pipelined form of 2^19 / 2^20: one workgroup per CU, but the A tile of the NEXT ticket is requested early: 3 windows measured +2.7 % over 2)
-	uint64_t marginPct = d.fusedMarginPct ? d.fusedMarginPct : ((wgPerCu >= 2 || (!dp && j.N <= (1ull << 20))) ? 300 : 200);
+	uint64_t marginPct = d.sw.fusedMarginPct ? d.sw.fusedMarginPct : ((wgPerCu >= 2 || (!dp && j.N <= (1ull << 20))) ? 300 : 200);
 	uint64_t Q = 1, X = 1, D = 1, NS = 1, Cq = C;
 	auto shape = [&](uint64_t q, uint64_t pct) {
 		Q = q; Cq = (C + Q - 1) / Q;
 		X = ((wgs / Q) * pct / 100 + tpc - 1) / tpc;
 		if (X < 1) X = 1;
-		D = d.fusedLag ? d.fusedLag : 1 + X;
-		NS = d.fusedRing ? d.fusedRing : D + 1 + X;
+		D = d.sw.fusedLag ? d.sw.fusedLag : 1 + X;
+		NS = d.sw.fusedRing ? d.sw.fusedRing : D + 1 + X;
 		if (NS <= D) NS = D + 1;
 		if (NS > Cq) NS = Cq; // fewer chunks than ring slots: no slot is ever reused
 		if (D > Cq) D = Cq;   // (then every A tile of the queue precedes its first B tile)
 		if (NS < 1) NS = 1;
 		return Q * NS * G * fftBytes;
 	};
-	if (d.fusedQueues) (void)shape(std::min<uint64_t>(std::min<uint64_t>(d.fusedQueues, kFusedMaxQueues), C), marginPct);
+	if (d.sw.fusedQueues) (void)shape(std::min<uint64_t>(std::min<uint64_t>(d.sw.fusedQueues, kFusedMaxQueues), C), marginPct);
 	else {
 		const uint64_t q8 = C >= 4 * kFusedMaxQueues ? kFusedMaxQueues : 1;
 		if (shape(q8, marginPct) > ringBudget && q8 > 1) (void)shape(1, marginPct);
-		while (!d.fusedMarginPct && shape(Q, marginPct) > ringBudget && marginPct > 50) marginPct -= 25;
+		while (!d.sw.fusedMarginPct && shape(Q, marginPct) > ringBudget && marginPct > 50) marginPct -= 25;
 	}
 	const uint64_t scratch = Q * NS * G * fftBytes;
 	if (d.userTempBytes && scratch > d.userTempBytes) return false;
@@ -1149,7 +1148,7 @@ static bool emit_fused(const TransformDesc& d, const AxisJob& j, Arena& ar, Dire
 	f.n0 = (uint32_t)n0; f.n1 = (uint32_t)n1; f.batch = (uint32_t)batch;
 	f.logG = logG; f.logTiles = logTiles; f.C = (uint32_t)C; f.NS = (uint32_t)NS; f.D = (uint32_t)D; f.Q = (uint32_t)Q;
 	f.swapIn = f.swapOut = j.inverse ? 1 : 0; f.reverse = 0; f.scale = j.scale;
-	pp.fusedWgPerCu = (int)d.fusedWgPerCu;
+	pp.fusedWgPerCu = (int)d.sw.fusedWgPerCu; pp.fusedProfile = d.sw.fusedProfile;
 	passes.push_back(pp);
 	out.uploadsPerAxis[j.axisIndex] = 2;
 	out.axisSplit[j.axisIndex][0] = n1; out.axisSplit[j.axisIndex][1] = n0;
@@ -1183,33 +1182,33 @@ static bool build_mix_fused_pass(const TransformDesc& d, bool dp, uint64_t M, co
 	const uint64_t n0 = (uint64_t)v.n0, n1 = (uint64_t)v.n1;
 	const uint64_t tilesA = (n1 + (uint64_t)v.tca - 1) / (uint64_t)v.tca, tilesB = (n0 + (uint64_t)v.tcb - 1) / (uint64_t)v.tcb, tiles = std::max(tilesA, tilesB);
 	const uint64_t fftBytes = ((n0 + 15) & ~15ull) * n1 * es; // a transform's share of a ring slot: n1 columns at a pitch of n0 rounded up to 16 elements (kernel_mix_fused.h NAP)
-	const uint64_t chunkTarget = d.fusedChunkBytes ? d.fusedChunkBytes : (1ull << 20);
+	const uint64_t chunkTarget = d.sw.fusedChunkBytes ? d.sw.fusedChunkBytes : (1ull << 20);
 	uint32_t logG = 0;
 	while ((fftBytes << (logG + 1)) <= chunkTarget && (1ull << (logG + 1)) <= batch) logG++;
 	const uint64_t G = 1ull << logG;
 	const uint64_t C = (batch + G - 1) / G;
 	const uint64_t tpc = tiles << logG;
 	const uint64_t ringBudget = fftBytes >= (32ull << 20) ? (256ull << 20) : (224ull << 20);
-	const uint64_t wgs = 256ull * (uint64_t)(d.fusedWgPerCu ? d.fusedWgPerCu : v.wgPerCu);
-	uint64_t marginPct = d.fusedMarginPct ? d.fusedMarginPct : (v.wgPerCu >= 2 ? 300 : 200);
+	const uint64_t wgs = 256ull * (uint64_t)(d.sw.fusedWgPerCu ? d.sw.fusedWgPerCu : v.wgPerCu);
+	uint64_t marginPct = d.sw.fusedMarginPct ? d.sw.fusedMarginPct : (v.wgPerCu >= 2 ? 300 : 200);
 	uint64_t Q = 1, X = 1, D = 1, NS = 1, Cq = C;
 	auto shape = [&](uint64_t q, uint64_t pct) {
 		Q = q; Cq = (C + Q - 1) / Q;
 		X = ((wgs / Q) * pct / 100 + tpc - 1) / tpc;
 		if (X < 1) X = 1;
-		D = d.fusedLag ? d.fusedLag : 1 + X;
-		NS = d.fusedRing ? d.fusedRing : D + 1 + X;
+		D = d.sw.fusedLag ? d.sw.fusedLag : 1 + X;
+		NS = d.sw.fusedRing ? d.sw.fusedRing : D + 1 + X;
 		if (NS <= D) NS = D + 1;
 		if (NS > Cq) NS = Cq;
 		if (D > Cq) D = Cq;
 		if (NS < 1) NS = 1;
 		return Q * NS * G * fftBytes;
 	};
-	if (d.fusedQueues) (void)shape(std::min<uint64_t>(std::min<uint64_t>(d.fusedQueues, kFusedMaxQueues), C), marginPct);
+	if (d.sw.fusedQueues) (void)shape(std::min<uint64_t>(std::min<uint64_t>(d.sw.fusedQueues, kFusedMaxQueues), C), marginPct);
 	else {
 		const uint64_t q8 = C >= 4 * kFusedMaxQueues ? kFusedMaxQueues : 1;
 		if (shape(q8, marginPct) > ringBudget && q8 > 1) (void)shape(1, marginPct);
-		while (!d.fusedMarginPct && shape(Q, marginPct) > ringBudget && marginPct > 50) marginPct -= 25;
+		while (!d.sw.fusedMarginPct && shape(Q, marginPct) > ringBudget && marginPct > 50) marginPct -= 25;
 	}
 	scratch = Q * NS * G * fftBytes;
 	if ((Cq + D) * tpc >= (1ull << 31)) return false; // 32-bit tickets
@@ -1236,7 +1235,7 @@ static bool build_mix_fused_pass(const TransformDesc& d, bool dp, uint64_t M, co
 	f.logG = logG; f.logTiles = 0; f.tiles = (uint32_t)tiles; f.tpc = (uint32_t)tpc;
 	f.C = (uint32_t)C; f.NS = (uint32_t)NS; f.D = (uint32_t)D; f.Q = (uint32_t)Q;
 	f.swapIn = f.swapOut = inverse ? 1 : 0; f.reverse = 0; f.scale = scale;
-	pp.fusedWgPerCu = (int)d.fusedWgPerCu;
+	pp.fusedWgPerCu = (int)d.sw.fusedWgPerCu; pp.fusedProfile = d.sw.fusedProfile;
 	return true;
 }
 // the other dimensions of an axis job as ONE batch progression (what a fused launch can follow)
@@ -1251,10 +1250,10 @@ static bool one_batch_progression(const AxisJob& j, uint64_t& batch, int64_t& in
 }
 // Returns false when no instance serves the length or the plan does not qualify (the caller emits separate passes).
 static bool emit_mix_fused(const TransformDesc& d, const AxisJob& j, Arena& ar, DirectionPlan& out, std::vector<PassPlan>& passes) {
-	if (!d.fused || d.disableFastKernels || (j.N & (j.N - 1)) == 0 || j.inStrideJ != 1 || j.outStrideJ != 1) return false;
-	if (const char* e = getenv("VKFFT_MI355X_MIXFUSED")) { if (atoi(e) == 0) return false; }
+	if (!d.sw.fused || d.disableFastKernels || (j.N & (j.N - 1)) == 0 || j.inStrideJ != 1 || j.outStrideJ != 1) return false;
+	if (d.sw.mixFused == 0) return false;
 	MixFusedShape v;
-	if (!mix_fused_lookup(j.N, j.dp, &v.variant, &v.n0, &v.n1, v.radA, v.radB, &v.tca, &v.tcb, &v.thr, &v.wgPerCu)) return false;
+	if (!mix_fused_lookup(j.N, j.dp, d.sw.mixFusedShape, &v.variant, &v.n0, &v.n1, v.radA, v.radB, &v.tca, &v.tcb, &v.thr, &v.wgPerCu)) return false;
 	uint64_t batch; int64_t inS, outS;
 	if (!one_batch_progression(j, batch, inS, outS)) return false;
 	PassPlan pp; uint64_t scratch = 0;
@@ -1274,16 +1273,16 @@ static void make_bluestein_tables(uint64_t N, uint64_t M, bool dp, Arena& ar, si
 // transform with the second chirp on its stores and nothing stored beyond N.  Reference: vkFFT_Scheduler.h:2406-2578 (multi-upload Bluestein), vkFFT_Bluestein.h:32,201.
 constexpr uint64_t kMixFusedBlueQuery = 1ull << 63; // (kernels_mixfused.hip: mix_fused_lookup(n | this) = the smallest chirp-z instance of n points or more)
 static bool emit_mix_fused_blue(const TransformDesc& d, const AxisJob& j, Arena& ar, DirectionPlan& out, std::vector<PassPlan>& passes) {
-	if (!d.fused || d.disableFastKernels || j.dp || j.inStrideJ != 1 || j.outStrideJ != 1 || d.forceBluesteinSize || d.fixMaxRadixBluestein) return false;
+	if (!d.sw.fused || d.disableFastKernels || j.dp || j.inStrideJ != 1 || j.outStrideJ != 1 || d.forceBluesteinSize || d.fixMaxRadixBluestein) return false;
 	if (j.inRole == ROLE_TEMP2 || j.outRole == ROLE_TEMP2) return false; // (an inner plan of a wrapped transform: its rows live where this plan keeps its spectrum)
-	if (const char* e = getenv("VKFFT_MI355X_MIXFUSED")) { if (atoi(e) == 0) return false; }
+	if (d.sw.mixFused == 0) return false;
 	// Measured on the device (profiles/r06_chirp_z_two_fused_launches_vs_separate_passes.jsonl): correct, and SLOWER than the three / five separate passes on a power of
 	// two it was built to replace (524309: 157 against 256 GB/s, 15319: 530 against 764) — two launches still move the padded sequence through memory four times,
 	// and the instances with the hooks sit at the 128-register cap.  Off unless asked for; what would win is ONE launch with both intermediates in the ring.
-	{ const char* e = getenv("VKFFT_MI355X_MIXFUSED_BLUE"); if (!e || atoi(e) == 0) return false; }
+	if (d.sw.mixFusedBlue == 0) return false;
 	const uint64_t N = j.N;
 	MixFusedShape v;
-	if (!mix_fused_lookup((2 * N - 1) | kMixFusedBlueQuery, false, &v.variant, &v.n0, &v.n1, v.radA, v.radB, &v.tca, &v.tcb, &v.thr, &v.wgPerCu)) return false;
+	if (!mix_fused_lookup((2 * N - 1) | kMixFusedBlueQuery, false, 0, &v.variant, &v.n0, &v.n1, v.radA, v.radB, &v.tca, &v.tcb, &v.thr, &v.wgPerCu)) return false;
 	const uint64_t M = (uint64_t)v.n0 * (uint64_t)v.n1;
 	uint64_t batch; int64_t inS, outS;
 	if (!one_batch_progression(j, batch, inS, outS)) return false;
@@ -1408,7 +1407,7 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 	const bool unit = j.inStrideJ == 1 && j.outStrideJ == 1;
 	bool smoothOK = is_supported_len(j.N, dmax);
 	const uint64_t rowCap = max_row_len(dp, d.maxLds);
-	PassBuild b;
+	PassBuild b(d.sw);
 	b.dp = dp; b.maxLds = d.maxLds; b.raderDirectMax = dmax; b.allowFast = !d.disableFastKernels; b.allowOp = !d.disableFastKernels;
 	b.inRole = j.inRole; b.outRole = j.outRole;
 	out.axisSplit[j.axisIndex][0] = j.N;
@@ -1444,7 +1443,7 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 		const uint64_t rowPitch = j.others.empty() ? j.N : (uint64_t)std::max<int64_t>(std::llabs(j.others[0].inStride), std::llabs(j.others[0].outStride));
 		uint64_t Mp = 64; while (Mp < 2 * j.N - 1) Mp *= 2; // measured: the power-of-two padded length wins even at 1.6x the {1,3,5}*2^k one
 		int v, bits[4], fpw, thr;
-		if ((rowPitch * 64 + j.N) * (dp ? 16 : 8) < 0x7FFFFF00ull && pow2_blue_lookup(ilog2(Mp), dp, &v, bits, &fpw, &thr)) fusedM = Mp;
+		if ((rowPitch * 64 + j.N) * (dp ? 16 : 8) < kSpanLimit && pow2_blue_lookup(ilog2(Mp), dp, Switches::shape(d.sw.pow2BlueShape, ilog2(Mp)), &v, bits, &fpw, &thr)) fusedM = Mp;
 	}
 	if (!unit && !nativeInstance && !d.disableFastKernels && !d.forceBluesteinSize && !d.fixMaxRadixBluestein && !smooth13(j.N) && !j.others.empty()
 	    && j.others[0].inStride == 1 && j.others[0].outStride == 1) {
@@ -1466,10 +1465,10 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 		// taken where it is faster than the fused Bluestein kernel on the next power of two M2 >= 2N - 1 (every served length forced either way on the device).  A point of
 		// the row costs c points of the padded power-of-two transform; Bluestein's 8192-point rows leave one workgroup per CU: 1.5 per point
 		uint64_t M2 = 64; while (M2 < 2 * j.N - 1) M2 *= 2;
-		const bool radForced = getenv("VKFFT_MI355X_MIXRAD") && atoi(getenv("VKFFT_MI355X_MIXRAD")) == 2; // (tests: always)
-		bool radTake = mixrad_choose(j.N, dp, false, mr) && (rowPitch * 64 + j.N) * (dp ? 16 : 8) < 0x7FFFFF00ull;
+		const bool radForced = d.sw.mixrad == 2; // (tests: always)
+		bool radTake = mixrad_choose(d.sw, j.N, dp, false, mr) && (rowPitch * 64 + j.N) * (dp ? 16 : 8) < kSpanLimit;
 		if (radTake) {
-			const double c = getenv("VKFFT_MI355X_MIXRAD_COST") ? atof(getenv("VKFFT_MI355X_MIXRAD_COST")) : mr.cost;
+			const double c = d.sw.mixradCost != d.sw.mixradCost ? mr.cost : d.sw.mixradCost; // (unset: the model)
 			radTake = radForced || c * (double)j.N < (double)M2 * (M2 >= 8192 ? 1.5 : 1.0);
 		}
 		if (radTake) {
@@ -1495,17 +1494,16 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 	struct { bool use = false, rader = false, col = false; int variant = -1; uint64_t len = 0; int rad[5] = {1, 1, 1, 1, 1}; int fpw = 0, thr = 0; } mc;
 	const bool colTile = !unit && !j.others.empty() && j.others[0].inStride == 1 && j.others[0].outStride == 1;
 	if ((unit || colTile) && !nativeInstance && !d.disableFastKernels && !d.forceBluesteinSize && !d.fixMaxRadixBluestein && (!smooth13(j.N) || (unit && smoothNoInstance))) {
-		const int mode = getenv("VKFFT_MI355X_MIXCONV") ? atoi(getenv("VKFFT_MI355X_MIXCONV")) : 1; // (read per plan: tests switch it)
+		const int mode = d.sw.mixconv;
 		// measured (tools/tune_mixconv.py, profiles/r03_mixconv_*): time per point relative to the power-of-two kernels
-		const double kCostRader = getenv("VKFFT_MI355X_MIXCONV_COST_RADER") ? atof(getenv("VKFFT_MI355X_MIXCONV_COST_RADER")) : 1.9;
-		const double kCostBlue = getenv("VKFFT_MI355X_MIXCONV_COST_BLUE") ? atof(getenv("VKFFT_MI355X_MIXCONV_COST_BLUE")) : 1.6;
+		const double kCostRader = d.sw.mixconvCostRader, kCostBlue = d.sw.mixconvCostBlue;
 		const double kPow2Big = 1.9; // the power-of-two kernel at its longest padded length (128 KiB per row, one workgroup per CU) costs that much more per point
 		const uint64_t esz = dp ? 16 : 8;
 		bool spanOK;
 		if (unit) {
 			const uint64_t rowPitch = j.others.empty() ? j.N : (uint64_t)std::max<int64_t>(std::llabs(j.others[0].inStride), std::llabs(j.others[0].outStride));
-			spanOK = (rowPitch * 64 + j.N) * esz < 0x7FFFFF00ull;
-		} else spanOK = (2 * j.N * (uint64_t)std::max<int64_t>(std::llabs(j.inStrideJ), std::llabs(j.outStrideJ)) + 64) * esz < 0x7FFFFF00ull;
+			spanOK = (rowPitch * 64 + j.N) * esz < kSpanLimit;
+		} else spanOK = (2 * j.N * (uint64_t)std::max<int64_t>(std::llabs(j.inStrideJ), std::llabs(j.outStrideJ)) + 64) * esz < kSpanLimit;
 		if (mode && spanOK) {
 			double best = fusedM && mode < 2 ? (double)fusedM * (fusedM * esz >= (128ull << 10) ? kPow2Big : 1.0) : 1e300;
 			int v, r5[5], f, t; uint64_t len;
@@ -1556,7 +1554,7 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 		int v, bits[4], fpw, thr;
 		const uint64_t C = j.others[0].count;
 		uint64_t outer = 1; for (size_t i = 1; i < j.others.size(); i++) outer *= j.others[i].count;
-		if (pow2_blue_lookup(ilog2(Mp), dp, &v, bits, &fpw, &thr) && C * j.N * outer < (1ull << 40)) {
+		if (pow2_blue_lookup(ilog2(Mp), dp, Switches::shape(d.sw.pow2BlueShape, ilog2(Mp)), &v, bits, &fpw, &thr) && C * j.N * outer < (1ull << 40)) {
 			const size_t mark = passes.size();
 			auto transpose = [&](bool back) {
 				PassPlan t; memset(&t.prm, 0, sizeof(t.prm));
@@ -1678,7 +1676,7 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 			// three factors: five passes (see pow2_col_blue_kernel) instead of the seven of two Four-Step transforms + multiply
 			const uint64_t n0 = spM[0], n1 = spM[1], n2 = spM[2], M1 = n1 * n2;
 			int v1, v3, v4, v5, vb, bits1[4], bits3[4], bits4[4], bits5[4], bitsb[4], tc1, tc3, tc4, tc5, tcb, th1, th3, th4, th5, thb;
-			if (pow2_col_blue_lookup(ilog2(n0), dp, 1, &v1, bits1, &tc1, &th1) && pow2_col_lookup(ilog2(n1), dp, &vb, bitsb, &tcb, &thb)
+			if (pow2_col_blue_lookup(ilog2(n0), dp, 1, &v1, bits1, &tc1, &th1) && pow2_col_lookup(ilog2(n1), dp, Switches::shape(d.sw.pow2ColShape, ilog2(n1)), &vb, bitsb, &tcb, &thb)
 			    && pow2_col_blue_lookup(ilog2(n2), dp, 2, &v3, bits3, &tc3, &th3) && pow2_col_blue_lookup(ilog2(n1), dp, 4, &v4, bits4, &tc4, &th4)
 			    && pow2_col_blue_lookup(ilog2(n0), dp, 3, &v5, bits5, &tc5, &th5)) {
 				uint64_t nsub = 1;
@@ -1783,36 +1781,36 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 		int variant, bits[4], tc, thr, rad5[5], fpw;
 		const bool p2 = (j.N & (j.N - 1)) == 0;
 		std::vector<uint64_t> probe;
-		if (!(p2 && pow2_col_lookup(ilog2(j.N), dp, &variant, bits, &tc, &thr)) && !opfft_lookup(j.N, dp, true, false, 0, 0, &variant, rad5, &fpw, &thr) &&
+		if (!(p2 && pow2_col_lookup(ilog2(j.N), dp, Switches::shape(d.sw.pow2ColShape, ilog2(j.N)), &variant, bits, &tc, &thr)) && !opfft_lookup(j.N, dp, true, false, 0, 0, &variant, rad5, &fpw, &thr) &&
 		    choose_split(j.N, dp, d.maxLds, dmax, true, probe)) {
 			if (padded) return kPadUnsupported; // (two passes: no kernel of that plan skips elements)
 			singleCap = 2048;
 		}
 	}
 	// 2^15 fp32 as ONE pass of the register-lean row kernel (measured 4.2 TB/s against 3.2 for the fused two-pass kernel); VKFFT_MI355X_ROW15=0: two passes
-	const bool row15 = !(getenv("VKFFT_MI355X_ROW15") && atoi(getenv("VKFFT_MI355X_ROW15")) == 0);
+	const bool row15 = d.sw.row15 != 0;
 	// (a power-of-two row beyond the interpreter's reach takes this branch only when its register-resident kernel is really there — table entry and 32-bit
 	// span —: otherwise the interpreter would be handed a row that does not fit LDS (error 3002) instead of the Four-Step plan below)
 	bool p2rowOK = false;
 	if (unit && !d.disableFastKernels && (j.N & (j.N - 1)) == 0 && j.N >= 4 && j.N <= (dp ? 8192u : (row15 ? 32768u : 16384u))) {
 		int variant, bits[4], fpw, thr;
 		const uint64_t rowPitch = j.others.empty() ? j.N : (uint64_t)std::max<int64_t>(std::llabs(j.others[0].inStride), std::llabs(j.others[0].outStride));
-		p2rowOK = (rowPitch * 64 + j.N) * (dp ? 16 : 8) < 0x7FFFFF00ull && pow2_row_lookup(ilog2(j.N), dp, &variant, bits, &fpw, &thr, padded);
+		p2rowOK = (rowPitch * 64 + j.N) * (dp ? 16 : 8) < kSpanLimit && pow2_row_lookup(ilog2(j.N), dp, Switches::shape(d.sw.pow2RowShape, ilog2(j.N)), &variant, bits, &fpw, &thr, padded);
 	}
 	// ... and the hand-written long rows of the mixed-radix family (mixed_table_6.inc: 11^4, 5^6, 7^5 in ONE LDS buffer of 117-151 KB, one workgroup per CU): one pass where
 	// the Four-Step plan would take two (VKFFT_MI355X_LONGROWS=0: the fused Four-Step launch of kernel_mix_fused.h instead)
 	bool mixLongOK = false;
-	if (unit && !padded && !d.disableFastKernels && (j.N & (j.N - 1)) != 0 && j.N > singleCap && j.N <= (dp ? 8192u : 16807u) && !(getenv("VKFFT_MI355X_LONGROWS") && atoi(getenv("VKFFT_MI355X_LONGROWS")) == 0)) {
+	if (unit && !padded && !d.disableFastKernels && (j.N & (j.N - 1)) != 0 && j.N > singleCap && j.N <= (dp ? 8192u : 16807u) && d.sw.longRows != 0) {
 		int variant, rad5[5], fpw, thr;
 		const uint64_t rowPitch = j.others.empty() ? j.N : (uint64_t)std::max<int64_t>(std::llabs(j.others[0].inStride), std::llabs(j.others[0].outStride));
-		mixLongOK = (rowPitch * 64 + j.N) * (dp ? 16 : 8) < 0x7FFFFF00ull && mixed_row_lookup(j.N, dp, &variant, rad5, &fpw, &thr);
+		mixLongOK = (rowPitch * 64 + j.N) * (dp ? 16 : 8) < kSpanLimit && mixed_row_lookup(j.N, dp, &variant, rad5, &fpw, &thr);
 	}
 	if (j.N <= singleCap || p2rowOK || mixLongOK) {
 		b.L = j.N;
 		if (unit && !padded && !d.disableFastKernels && ((j.N & (j.N - 1)) != 0 || j.N == 2)) { // curated non-power-of-two lengths (and N = 2): hand-specialised mixed-radix kernel
 			int variant, rad5[5], fpw, thr;
 			uint64_t rowPitch = j.others.empty() ? j.N : (uint64_t)std::max<int64_t>(std::llabs(j.others[0].inStride), std::llabs(j.others[0].outStride));
-			if ((rowPitch * 64 + j.N) * (dp ? 16 : 8) < 0x7FFFFF00ull && mixed_row_lookup(j.N, dp, &variant, rad5, &fpw, &thr)) {
+			if ((rowPitch * 64 + j.N) * (dp ? 16 : 8) < kSpanLimit && mixed_row_lookup(j.N, dp, &variant, rad5, &fpw, &thr)) {
 				b.fastKernel = KERNEL_MIXED_ROW; b.fastVariant = variant; b.fastThreads = thr; b.forceT = (uint32_t)fpw;
 				for (int k = 0; k < 5; k++) if (rad5[k] > 1) b.radices.push_back((uint32_t)rad5[k]);
 			}
@@ -1820,7 +1818,7 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 		if (unit && !d.disableFastKernels && (j.N & (j.N - 1)) == 0 && j.N >= 4) {
 			int variant, bits[4], fpw, thr;
 			uint64_t rowPitch = j.others.empty() ? j.N : (uint64_t)std::max<int64_t>(std::llabs(j.others[0].inStride), std::llabs(j.others[0].outStride));
-			if ((rowPitch * 64 + j.N) * (dp ? 16 : 8) < 0x7FFFFF00ull && pow2_row_lookup(ilog2(j.N), dp, &variant, bits, &fpw, &thr, padded)) {
+			if ((rowPitch * 64 + j.N) * (dp ? 16 : 8) < kSpanLimit && pow2_row_lookup(ilog2(j.N), dp, Switches::shape(d.sw.pow2RowShape, ilog2(j.N)), &variant, bits, &fpw, &thr, padded)) {
 				b.fastKernel = KERNEL_POW2_ROW; b.fastVariant = variant; b.fastThreads = thr; b.forceT = (uint32_t)fpw;
 				for (int k = 0; k < 4; k++) if (bits[k]) b.radices.push_back(1u << bits[k]);
 			}
@@ -1906,7 +1904,7 @@ static int make_r2c_pair_pass(uint64_t N, bool dp, bool inverse, const std::vect
 // Real rows whose complex length has a prime factor above 31 that the interpreter would take as a direct O(p^2) Rader stage (47, 59: p - 1 is not smooth) or
 // that no instance kernel serves (a Rader prime with an unserved cofactor): measured at 0.12-0.26x the reference (R2C / DCT rows of 94, 118, 235, 295, 376
 // reals, profiles/r04_*_rows_*) — the fused Bluestein kernel of the real transforms (kernel_blue_r2r.h) takes them instead.
-static bool real_row_prefers_bluestein(uint64_t L, bool dp) {
+static bool real_row_prefers_bluestein(const Switches& sw, uint64_t L, bool dp) {
 	if (L < 2 || L > 4096) return false;
 	uint64_t P = 0, rest = L;
 	for (uint64_t q = 2; q * q <= rest; q++) while (rest % q == 0) { P = q; rest /= q; }
@@ -1916,7 +1914,7 @@ static bool real_row_prefers_bluestein(uint64_t L, bool dp) {
 	if (mixed_row_lookup(L, dp, &v, r5, &f, &t)) return false;
 	if (P == L) return !mixconv_lookup(true, false, P, dp, &v, &len, r5, &f, &t);
 	MixradChoice mr;
-	return !mixrad_choose(L, dp, true, mr);
+	return !mixrad_choose(sw, L, dp, true, mr);
 }
 
 // ---- real transforms: coverage path -------------------------------------------------------------------------
@@ -1993,19 +1991,19 @@ static uint64_t pairable_rows(const std::vector<HostDim>& others) {
 }
 // a unit-stride fp32 row longer than the two-buffer single-pass limit that has one of the long instances of tools/gen_long_rows_table.py (one LDS buffer, one workgroup per CU)
 static bool long_row_instance(const TransformDesc& d, uint64_t L, bool dp) {
-	if (d.disableFastKernels || L <= max_row_len(dp, d.maxLds) || L > (dp ? 8192u : 16807u) || (getenv("VKFFT_MI355X_LONGROWS") && atoi(getenv("VKFFT_MI355X_LONGROWS")) == 0)) return false;
+	if (d.disableFastKernels || L <= max_row_len(dp, d.maxLds) || L > (dp ? 8192u : 16807u) || d.sw.longRows == 0) return false;
 	int v, r5[5], f, t;
 	return mixed_row_lookup(L, dp, &v, r5, &f, &t);
 }
 static bool prefer_full_length_pairs(const TransformDesc& d, uint64_t N, bool unit, uint64_t rows, uint32_t preHalf, uint32_t postHalf, uint64_t halfLen) {
-	const int mode = getenv("VKFFT_MI355X_EVEN_FULL") ? atoi(getenv("VKFFT_MI355X_EVEN_FULL")) : 1;
+	const int mode = d.sw.evenFull;
 	if (N > max_row_len(d.dp, d.maxLds)) return false; // (the long rows keep their half-length forms: one workgroup per CU is no place for twice the points)
-	if (!mode || d.disableFastKernels || !unit || rows < 2 || getenv("VKFFT_MI355X_NO_TMAPS") || getenv("VKFFT_MI355X_NO_ROW_PAIRS") || getenv("VKFFT_MI355X_NO_MIXED_OPS")) return false;
+	if (!mode || d.disableFastKernels || !unit || rows < 2 || d.sw.noTmaps || d.sw.noRowPairs || d.sw.noMixedOps) return false;
 	int v, r5[5], f, t;
 	// (eight: the plain sides of R2C / C2R then move directly, kernel_mixed.h DIRECT; round 6: or the full length runs on the Rader-stage kernel, whose maps are the
 	// tables of the full-length forms only — the half-length complex form of 328 = 2 * 4 * 41 reals fell back to the interpreter: 0.17x the reference)
 	MixradChoice mr;
-	if (!(mixed_row_lookup(N, d.dp, &v, r5, &f, &t) && t / f >= 8) && !mixrad_choose(N, d.dp, true, mr)) return false;
+	if (!(mixed_row_lookup(N, d.dp, &v, r5, &f, &t) && t / f >= 8) && !mixrad_choose(d.sw, N, d.dp, true, mr)) return false;
 	if (mode == 1 && opfft_lookup(halfLen, d.dp, false, false, preHalf, postHalf, &v, r5, &f, &t)) return false;
 	return true;
 }
@@ -2050,7 +2048,7 @@ static int plan_r2c_axis0_fused(const TransformDesc& d, bool inverse, const std:
 	const bool padReal = usePad && !d.padFrequency;
 	if (usePad && !padReal) return kPadUnsupported; // (padding of the half spectrum along axis 0)
 	const uint32_t padL = padReal ? (uint32_t)d.padL[0] : 0u, padN = padReal ? (uint32_t)(d.padR[0] - d.padL[0]) : 0u;
-	PassBuild b;
+	PassBuild b(d.sw);
 	b.dp = dp; b.maxLds = d.maxLds; b.raderDirectMax = dmax; b.allowFast = false; b.allowOp = !d.disableFastKernels;
 	b.opN = (uint32_t)N; b.scale = scale;
 	bool even = (N % 2 == 0);
@@ -2063,12 +2061,12 @@ static int plan_r2c_axis0_fused(const TransformDesc& d, bool inverse, const std:
 	int blueVariant = 0, blueBits[4] = {0, 0, 0, 0}, blueFpw = 0, blueThr = 0;
 	if (padReal && (!is_supported_len(b.L, dmax) || b.L > max_row_len(dp, d.maxLds))) return kPadUnsupported;
 	bool blueByChoice = false; // the length is within the interpreter's reach, the fused Bluestein kernel is the faster form (real_row_prefers_bluestein)
-	if (is_supported_len(b.L, dmax) && !d.disableFastKernels && !padReal && real_row_prefers_bluestein(b.L, dp) && !getenv("VKFFT_MI355X_NO_REAL_BLUE_CHOICE")) {
+	if (is_supported_len(b.L, dmax) && !d.disableFastKernels && !padReal && real_row_prefers_bluestein(d.sw, b.L, dp) && !d.sw.noRealBlueChoice) {
 		uint64_t Mp = 64; while (Mp < 2 * N - 1) Mp *= 2;
 		uint64_t pitch = N + 2;
 		if (!othersReal.empty()) pitch = (uint64_t)std::max<int64_t>(std::llabs(othersReal[0].inStride), 2 * std::llabs(othersCplx[0].inStride));
 		int v, bits[4], fpw, thr;
-		blueByChoice = Mp <= (dp ? 4096u : 8192u) && (pitch * 64 + 2 * N) * (dp ? 8 : 4) < 0x7FFFFF00ull && pow2_blue_r2r_lookup(ilog2(Mp), dp, inverse ? OP_C2R_FULL : OP_R2C_FULL, &v, bits, &fpw, &thr);
+		blueByChoice = Mp <= (dp ? 4096u : 8192u) && (pitch * 64 + 2 * N) * (dp ? 8 : 4) < kSpanLimit && pow2_blue_r2r_lookup(ilog2(Mp), dp, inverse ? OP_C2R_FULL : OP_R2C_FULL, &v, bits, &fpw, &thr);
 	}
 	if (!is_supported_len(b.L, dmax) || blueByChoice) {
 		// the (half) length has a prime factor outside the radix / Rader stages: full-length "callback" form (real -> (x, 0),
@@ -2108,7 +2106,7 @@ static int plan_r2c_axis0_fused(const TransformDesc& d, bool inverse, const std:
 		}
 		uint64_t pitch = N + 2;
 		if (!othersReal.empty()) pitch = (uint64_t)std::max<int64_t>(std::llabs(othersReal[0].inStride), 2 * std::llabs(othersCplx[0].inStride));
-		if ((pitch * 64 + 2 * N) * (dp ? 8 : 4) >= 0x7FFFFF00ull) return 3003; // 32-bit buffer offsets inside a tile of rows
+		if ((pitch * 64 + 2 * N) * (dp ? 8 : 4) >= kSpanLimit) return 3003; // 32-bit buffer offsets inside a tile of rows
 		if (!pow2_blue_r2r_lookup(ilog2(Mp), dp, inverse ? OP_C2R_FULL : OP_R2C_FULL, &blueVariant, blueBits, &blueFpw, &blueThr)) return 3003;
 		blueM = Mp; even = false; b.L = N;
 	}
@@ -2137,7 +2135,7 @@ static int plan_r2c_axis0_fused(const TransformDesc& d, bool inverse, const std:
 			io.firstPre = inverse ? OP_C2R_FULL : OP_R2C_FULL; io.lastPost = io.firstPre;
 			io.natural = true; io.firstRealIn = !inverse; io.lastRealOut = inverse;
 			io.natOutLen = (uint32_t)(inverse ? N : N / 2 + 1); io.opN = (uint32_t)N; io.blueN = (uint32_t)N;
-			PassBuild proto; proto.dp = dp; proto.maxLds = d.maxLds; proto.raderDirectMax = dmax; proto.allowFast = !d.disableFastKernels; proto.allowOp = !d.disableFastKernels;
+			PassBuild proto(d.sw); proto.dp = dp; proto.maxLds = d.maxLds; proto.raderDirectMax = dmax; proto.allowFast = !d.disableFastKernels; proto.allowOp = !d.disableFastKernels;
 			int r = emit_multipass(proto, N, sp, io, ar, passes); if (r) return r == 3002 ? 3003 : r;
 			uint64_t nsub = 1; for (auto& h : dims) nsub *= h.count;
 			out.tempBytes = std::max<uint64_t>(out.tempBytes, nsub * N * es);
@@ -2148,7 +2146,7 @@ static int plan_r2c_axis0_fused(const TransformDesc& d, bool inverse, const std:
 		const uint64_t H = N / 2;
 		std::vector<uint64_t> sp;
 		if (!choose_split(H, dp, d.maxLds, dmax, !d.disableFastKernels, sp)) return 3003;
-		PassBuild proto; proto.dp = dp; proto.maxLds = d.maxLds; proto.raderDirectMax = dmax; proto.allowFast = !d.disableFastKernels;
+		PassBuild proto(d.sw); proto.dp = dp; proto.maxLds = d.maxLds; proto.raderDirectMax = dmax; proto.allowFast = !d.disableFastKernels;
 		// pair pass descriptor (in place on the complex rows)
 		PassPlan pair;
 		if (int pr = make_r2c_pair_pass(N, dp, inverse, othersCplx, cplxRole, ar, pair)) return pr;
@@ -2245,7 +2243,7 @@ static int plan_r2r_axis_fused(const TransformDesc& d, int type, bool dst, uint6
 	const bool dp = d.dp;
 	const size_t es = dp ? 16 : 8;
 	const uint32_t dmax = direct_max(d);
-	PassBuild b;
+	PassBuild b(d.sw);
 	b.dp = dp; b.maxLds = d.maxLds; b.raderDirectMax = dmax; b.allowFast = false; b.allowOp = !d.disableFastKernels;
 	b.opN = (uint32_t)N; b.scale = scale;
 	b.realIn = b.realOut = true;
@@ -2327,13 +2325,13 @@ static int plan_r2r_axis_fused(const TransformDesc& d, int type, bool dst, uint6
 	}
 	b.label = dst ? "dst" : "dct";
 	bool blueByChoice = false; // within the interpreter's reach, but the fused Bluestein kernel is the faster form (real_row_prefers_bluestein)
-	if (is_supported_len(b.L, dmax) && unit && !d.disableFastKernels && real_row_prefers_bluestein(b.L, dp) && !getenv("VKFFT_MI355X_NO_REAL_BLUE_CHOICE")) {
+	if (is_supported_len(b.L, dmax) && unit && !d.disableFastKernels && real_row_prefers_bluestein(d.sw, b.L, dp) && !d.sw.noRealBlueChoice) {
 		const uint64_t Lb = (type == 2 || type == 3) ? N : b.L;
 		uint64_t Mp = 64; while (Mp < 2 * Lb - 1) Mp *= 2;
 		const uint64_t rowPitch = others.empty() ? N : (uint64_t)std::max<int64_t>(std::llabs(others[0].inStride), std::llabs(others[0].outStride));
 		const uint32_t pre = type == 2 ? (uint32_t)OP_DCT2_PRE : type == 3 ? (uint32_t)OP_DCT3_PRE : b.preOp;
 		int v, bits[4], fpw, thr;
-		blueByChoice = Mp <= (dp ? 4096u : 8192u) && (rowPitch * 64 + 2 * N) * (dp ? 8 : 4) < 0x7FFFFF00ull && pow2_blue_r2r_lookup(ilog2(Mp), dp, pre, &v, bits, &fpw, &thr);
+		blueByChoice = Mp <= (dp ? 4096u : 8192u) && (rowPitch * 64 + 2 * N) * (dp ? 8 : 4) < kSpanLimit && pow2_blue_r2r_lookup(ilog2(Mp), dp, pre, &v, bits, &fpw, &thr);
 	}
 	if (!is_supported_len(b.L, dmax) || blueByChoice) {
 		// the embedding length has a prime factor outside the radix / Rader stages (e.g. DST-I of 100: 202 = 2 * 101): the
@@ -2359,7 +2357,7 @@ static int plan_r2r_axis_fused(const TransformDesc& d, int type, bool dst, uint6
 		if (type == 4 && !dp && Mp > 8192) return 3004;
 		int variant, bits[4], fpw, thr;
 		const uint64_t rowPitch = others.empty() ? N : (uint64_t)std::max<int64_t>(std::llabs(others[0].inStride), std::llabs(others[0].outStride));
-		if ((rowPitch * 64 + 2 * N) * (dp ? 8 : 4) >= 0x7FFFFF00ull || !pow2_blue_r2r_lookup(ilog2(Mp), dp, b.preOp, &variant, bits, &fpw, &thr)) return 3004;
+		if ((rowPitch * 64 + 2 * N) * (dp ? 8 : 4) >= kSpanLimit || !pow2_blue_r2r_lookup(ilog2(Mp), dp, b.preOp, &variant, bits, &fpw, &thr)) return 3004;
 		size_t chirpOff, bhatOff;
 		make_bluestein_tables(Lb, Mp, dp, ar, chirpOff, bhatOff, true); // aux / aux2 stay with the real transform's own tables
 		b.L = Mp; b.blueN = (uint32_t)Lb;
@@ -2398,7 +2396,7 @@ static int plan_r2r_axis_fused(const TransformDesc& d, int type, bool dst, uint6
 		for (auto& o : io.othersOut) o.inStride = o.outStride;
 		io.inRole = inRole; io.outRole = outRole; io.scale = scale;
 		io.natural = true; io.firstRealIn = io.lastRealOut = true; io.natOutLen = (uint32_t)N; io.opN = (uint32_t)N; io.blueN = (uint32_t)Lm;
-		PassBuild proto; proto.dp = dp; proto.maxLds = d.maxLds; proto.raderDirectMax = dmax; proto.allowFast = !d.disableFastKernels; proto.allowOp = !d.disableFastKernels;
+		PassBuild proto(d.sw); proto.dp = dp; proto.maxLds = d.maxLds; proto.raderDirectMax = dmax; proto.allowFast = !d.disableFastKernels; proto.allowOp = !d.disableFastKernels;
 		int r = emit_multipass(proto, Lm, sp, io, ar, passes); if (r) return r == 3002 ? 3004 : r;
 		uint64_t nsub = 1; for (auto& o : others) nsub *= o.count;
 		out.tempBytes = std::max<uint64_t>(out.tempBytes, nsub * Lm * es);
@@ -2444,7 +2442,7 @@ int build_conv_axis_plan(const TransformDesc& d, const ConvAxisDesc& c, Directio
 	const int64_t strideJ = (int64_t)d.bufStride[a - 1], sys = (int64_t)d.bufStride[nd - 1];
 	const uint64_t W = d.kind == 1 ? d.size[0] / 2 + 1 : d.size[0];
 	// buffer addressing: a column tile and every kernel system behind it lie within one 2 GiB resource
-	if (((uint64_t)L * (uint64_t)strideJ + 64) * es + c.kernelSystems * (uint64_t)sys * es >= 0x7FFFFF00ull) return 3002;
+	if (((uint64_t)L * (uint64_t)strideJ + 64) * es + c.kernelSystems * (uint64_t)sys * es >= kSpanLimit) return 3002;
 	// the other spatial dimensions (between axis 0 and the last axis), then the systems: coordinates (inside the merged kernel) and batches
 	std::vector<HostDim> spatial; // strides in the data buffer
 	for (int o = 1; o < a; o++) spatial.push_back({d.size[o], (int64_t)d.bufStride[o - 1], (int64_t)d.bufStride[o - 1]});
@@ -2495,7 +2493,7 @@ int build_conv_axis_plan(const TransformDesc& d, const ConvAxisDesc& c, Directio
 	{ int64_t run = tSub; for (auto& h : spatial) { restData.push_back(h); restT.push_back({h.count, run, run}); run *= (int64_t)h.count; } }
 	restData.push_back({d.batch * c.coordinates, sys, sys}); restT.push_back({d.batch * c.coordinates, tSys, tSys});
 	{
-		PassBuild b;
+		PassBuild b(d.sw);
 		b.dp = dp; b.maxLds = d.maxLds; b.allowFast = true; b.allowOp = true;
 		b.L = n0; b.inStrideJ = (int64_t)M * strideJ; b.outStrideJ = (int64_t)M * tRow;
 		b.colIn = b.colOut = true;
