@@ -1,10 +1,59 @@
 """Convolution throughput next to the reference on the same box (same call): python tools/perf_conv.py  ->  JSON lines.
-Algorithmic bytes of one convolution append = read + write of the data systems + one read of the kernel systems."""
+Algorithmic bytes of one convolution append = read + write of the data systems + one read of the kernel systems.
+python tools/perf_conv.py rows: one-dimensional plans, the one-launch form (pow2_conv_row_kernel) against VKFFT_MI355X_CONV_SEPARATE=1 (three launches) in the same
+process, alternating, on one buffer of 256 MiB."""
 import ctypes as C, json, os, sys, time
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, root)
 import numpy as np, torch
 from vkfft_amd import api
+
+
+def rows_ab(n, dp, r2c, pad, mib=256, rounds=7, it=10):
+    """fused against separate passes: `rounds` alternating windows of `it` appends each, timed with device events; the kernel spectrum is all ones (the data stays
+    what it is however often the convolution runs)"""
+    rb = (n + 2 if r2c else 2 * n) * (8 if dp else 4)
+    rows = (mib << 20) // rb
+    rt = torch.float64 if dp else torch.float32
+    data = torch.rand((mib << 20) // (8 if dp else 4), device="cuda", dtype=rt)
+    kern = torch.zeros(2 * n + 4, device="cuda", dtype=rt); kern[0::2] = 1
+    kw = dict(buffer_ptr=data.data_ptr(), kernel=kern.data_ptr(), performConvolution=1, dp=dp, r2c=r2c, normalize=True)
+    if pad:
+        kw.update(performZeropadding=[1, 0, 0, 0], fft_zeropad_left=[n // 2, 0, 0, 0], fft_zeropad_right=[n, 0, 0, 0])
+    apps = {}
+    apps["fused"] = api.App([n], rows, **kw)
+    os.environ["VKFFT_MI355X_CONV_SEPARATE"] = "1"
+    try:
+        apps["separate"] = api.App([n], rows, **kw)
+    finally:
+        del os.environ["VKFFT_MI355X_CONV_SEPARATE"]
+    info = {k: a.launch_info() for k, a in apps.items()}
+    for a in apps.values():
+        for _ in range(3): a.forward()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in apps}
+    for _ in range(rounds):
+        for k, a in apps.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(it): a.forward()
+            e1.record(); torch.cuda.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / it)
+    for a in apps.values(): a.delete()
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    moved = 2 * rows * rb * (0.5 if pad else 1.0)  # bytes the algorithm owes: one read and one write of the (unpadded part of the) data
+    return dict(n=n, dp=dp, r2c=r2c, zero_padded_upper_half=bool(pad), rows=rows, launches={k: v[0] for k, v in info.items()}, kernel=info["fused"][1],
+                ms={k: round(v, 4) for k, v in med.items()}, ms_min_max={k: [round(min(v), 4), round(max(v), 4)] for k, v in ms.items()},
+                fused_alg_GBps=round(moved / med["fused"] / 1e6, 1), separate_alg_GBps=round(moved / med["separate"] / 1e6, 1),
+                speedup=round(med["separate"] / med["fused"], 3))
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "rows":
+    print(json.dumps(dict(source_hash=api.source_hash(), library_is_current=api.library_is_current(), device=torch.cuda.get_device_name(0))), flush=True)
+    for n, dp, r2c, pad in [(256, False, False, False), (1024, False, False, False), (4096, False, False, False), (256, False, True, False), (1024, False, True, False),
+                            (4096, False, True, False), (1024, True, False, False), (1024, True, True, False), (1024, False, False, True), (4096, False, True, True)]:
+        print(json.dumps(rows_ab(n, dp, r2c, pad)), flush=True)
+    sys.exit(0)
 ref = None
 p = os.path.join(root, "oracle", "_ref", "libvkfft_ref.so")
 if os.path.exists(p):

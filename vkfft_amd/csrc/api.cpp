@@ -33,6 +33,8 @@ struct AppState {
 	                               // convFwd / convInv then omit the axis (planner.cpp build_conv_axis_plan)
 	VkFFTApplication* convInvFull = nullptr; // merged form only: VkFFTAppend(app, 1) is a plain inverse over ALL axes; convInv lacks the merged one, so that
 	VkFFTConfiguration convInvFullCfg = {};  // direction gets its own application, created at its first use from this configuration
+	bool convRow = false;          // one-dimensional plan in ONE launch (pow2_conv_row_kernel): convMid is the whole convolution, there is no convFwd, and convInv —
+	                               // a plain inverse over the axis, built at plan creation — serves VkFFTAppend(app, 1) only
 	uint32_t zeroPadMask = 0;      // zero-padded axes whose plan cannot skip the range: it is written with zeros ahead of the transform that reads it
 };
 
@@ -122,11 +124,15 @@ VKFFT_API int vkfftMI355XDescribePlan(const VkFFTApplication* app, int inverse, 
 	size_t pos = 0;
 	int launches = 0;
 	const AppState* st = (const AppState*)app->impl;
-	if (st && st->convFwd) {
+	if (st && (st->convFwd || st->convRow)) {
+		if (st->convRow && inverse != 1) { // the whole convolution is one launch
+			if (names && cap) snprintf(names, (size_t)cap, "pow2_conv_row_kernel");
+			return 1;
+		}
 		// convolution application: what VkFFTAppend(app, -1) launches — forward transform (without the merged axis), the merged axis or the separate
 		// element-wise product, inverse transform of the results
 		if (inverse == 1) { // a plain inverse of the results (the merged form builds that application at its first use)
-			const VkFFTApplication* inv = st->convMid ? st->convInvFull : st->convInv;
+			const VkFFTApplication* inv = st->convMid && !st->convRow ? st->convInvFull : st->convInv;
 			if (inv) describe_passes(inv->localFFTPlan_inverse, names, cap, pos, launches);
 			return launches;
 		}
@@ -375,7 +381,7 @@ VKFFT_API VkFFTResult VkFFTAppend(VkFFTApplication* app, int inverse, VkFFTLaunc
 	VkFFTConfiguration& c = app->configuration;
 	AppState* st = (AppState*)app->impl;
 	if (st == nullptr) return VKFFT_ERROR_PLAN_NOT_INITIALIZED;
-	if (st->convFwd) return append_convolution(app, inverse, lp);
+	if (st->convFwd || st->convRow) return append_convolution(app, inverse, lp);
 	VkFFTPlan* pl;
 	if (inverse != 1) { // reference: anything but 1 is forward (vkFFT_RunApp.h:102-111)
 		if (!app->localFFTPlan) return VKFFT_ERROR_ONLY_INVERSE_FFT_INITIALIZED;
@@ -562,6 +568,43 @@ VkFFTResult initialize_convolution(VkFFTApplication* app, const VkFFTConfigurati
 			} else free_direction(pl);
 		} else { free(pl); delete dpl; }
 	}
+	// one-dimensional plan: the whole convolution in one launch of pow2_conv_row_kernel (kernel_pow2_conv.h) when an instance serves the row — dense rows of a
+	// power-of-two length in the buffer itself, every coordinate with its own kernel component, one kernel set.  Everything else keeps the three launches
+	// (VKFFT_MI355X_CONV_SEPARATE selects them here too)
+	if (in.FFTdim == 1 && m <= 1 && nk == 1 && !in.crossPowerSpectrumNormalization && !in.frequencyZeroPadding && !in.isInputFormatted && !sw.convSeparate &&
+	    !(in.performR2C && in.conjugateConvolution) && in.size[0] > 1) {
+		TransformDesc d;
+		d.fftDim = 1; d.size[0] = in.size[0];
+		d.batch = nb; d.dp = in.doublePrecision != 0; d.kind = in.performR2C ? 1 : 0;
+		d.bufStride[0] = in.bufferStride[0] ? in.bufferStride[0] : (in.performR2C ? d.size[0] / 2 + 1 : d.size[0]); // (the planner takes dense rows only)
+		if (in.performZeropadding[0] && in.fft_zeropad_right[0] > in.fft_zeropad_left[0]) { d.padL[0] = in.fft_zeropad_left[0]; d.padR[0] = in.fft_zeropad_right[0]; }
+		d.sw = sw;
+		d.disableFastKernels = sw.genericOnly;
+		if (in.sharedMemorySize && in.sharedMemorySize < 160 * 1024) d.disableFastKernels = true;
+		ConvAxisDesc cd;
+		cd.matrix = 1; cd.coordinates = (uint32_t)c.coordinateFeatures; cd.conjugate = (uint32_t)in.conjugateConvolution;
+		cd.kernelSystems = c.coordinateFeatures;
+		cd.scale = in.normalize ? 1.0 / (double)d.size[0] : 1.0;
+		VkFFTPlan* pl = (VkFFTPlan*)calloc(1, sizeof(VkFFTPlan));
+		DirectionPlan* dpl = new (std::nothrow) DirectionPlan();
+		if (pl && dpl) {
+			pl->impl = dpl;
+			if (build_conv_row_plan(d, cd, *dpl) == 0 && !dpl->arena.empty() && hipMalloc(&dpl->dArena, dpl->arena.size()) == hipSuccess &&
+			    hipMemcpy(dpl->dArena, dpl->arena.data(), dpl->arena.size(), hipMemcpyHostToDevice) == hipSuccess) {
+				st->convMid = pl; st->convRow = true;
+				if (in.printMemoryLayout || sw.printPlan) fprintf(stderr, "[vkfft_mi355x] convolution: axis 0 merged (forward, kernel product, inverse in one launch of pow2_conv_row_kernel, %u rows per workgroup%s)\n", dpl->passes[0].prm.T, in.performR2C ? ", two real rows per transform" : "");
+			} else free_direction(pl);
+		} else { free(pl); delete dpl; }
+	}
+	if (st->convRow) { // no forward application; the inverse one is the plain inverse over the axis (VkFFTAppend(app, 1)), built here like convInvFull below
+		st->convInv = (VkFFTApplication*)calloc(1, sizeof(VkFFTApplication));
+		if (!st->convInv) { deleteVkFFT(app); return VKFFT_ERROR_MALLOC_FAILED; }
+		VkFFTResult r1 = initializeVkFFT(st->convInv, b);
+		if (r1 != VKFFT_SUCCESS) { free(st->convInv); st->convInv = nullptr; deleteVkFFT(app); return r1; }
+		for (int i = 0; i < VKFFT_MAX_FFT_DIMENSIONS; i++) c.bufferStride[i] = st->convInv->configuration.bufferStride[i];
+		app->firstAxis = 0; app->lastAxis = 0;
+		return VKFFT_SUCCESS;
+	}
 	st->convFwd = (VkFFTApplication*)calloc(1, sizeof(VkFFTApplication));
 	st->convInv = (VkFFTApplication*)calloc(1, sizeof(VkFFTApplication));
 	if (!st->convFwd || !st->convInv) { deleteVkFFT(app); return VKFFT_ERROR_MALLOC_FAILED; }
@@ -594,7 +637,7 @@ VkFFTResult append_convolution(VkFFTApplication* app, int inverse, VkFFTLaunchPa
 	VkFFTLaunchParams inv = VKFFT_ZERO_INIT;
 	if (lp) { inv.buffer = lp->buffer; inv.tempBuffer = lp->tempBuffer; inv.bufferOffset = lp->bufferOffset; inv.tempBufferOffset = lp->tempBufferOffset; }
 	if (inverse == 1) { // a plain inverse of the numberKernels results, over every axis
-		if (!st->convMid) return VkFFTAppend(st->convInv, 1, lp ? &inv : nullptr);
+		if (!st->convMid || st->convRow) return VkFFTAppend(st->convInv, 1, lp ? &inv : nullptr);
 		if (!st->convInvFull) return VKFFT_ERROR_PLAN_NOT_INITIALIZED; // (built by initializeVkFFT: convInv omits the merged axis)
 		VkFFTLaunchParams full = inv;
 		if (!lp || !lp->buffer) full.buffer = c.buffer;
@@ -603,6 +646,14 @@ VkFFTResult append_convolution(VkFFTApplication* app, int inverse, VkFFTLaunchPa
 	}
 	if (c.kernel == nullptr || c.kernel[0] == nullptr) return VKFFT_ERROR_EMPTY_kernel;
 	if (c.buffer == nullptr || c.buffer[0] == nullptr) return VKFFT_ERROR_EMPTY_buffer;
+	if (st->convRow) { // the whole convolution: one launch on the caller's stream
+		LaunchBuffers lb;
+		lb.base[ROLE_BUFFER] = (char*)c.buffer[0] + c.bufferOffset;
+		lb.kernel = (const char*)c.kernel[0] + c.kernelOffset;
+		StreamSet ss;
+		if (c.stream && c.num_streams >= 1) ss.s[0] = c.stream[0];
+		return execute_direction(*(DirectionPlan*)st->convMid->impl, lb, ss, nullptr) ? VKFFT_ERROR_FAILED_TO_LAUNCH_KERNEL : VKFFT_SUCCESS;
+	}
 	VkFFTResult r = VkFFTAppend(st->convFwd, -1, lp);
 	if (r != VKFFT_SUCCESS) return r;
 	if (st->convMid) { // last axis forward, kernel product, last axis backwards: one pass

@@ -13,7 +13,7 @@ namespace vkfft_mi355x {
 
 // ROLE_TEMP2: a second scratch region behind ROLE_TEMP in the same allocation, for plans that wrap an inner plan which uses ROLE_TEMP itself
 enum BufRole : int { ROLE_BUFFER = 0, ROLE_TEMP = 1, ROLE_INPUT = 2, ROLE_OUTPUT = 3, ROLE_TEMP2 = 4 };
-enum KernelKind : int { KERNEL_GENERIC = 0, KERNEL_POW2_ROW = 1, KERNEL_POW2_COL = 2, KERNEL_R2C_PAIR = 3, KERNEL_MIXED_ROW = 5, KERNEL_OPFFT = 6, KERNEL_POW2_BLUE = 7, KERNEL_POW2_COL_BLUE = 8, KERNEL_POW2_BLUE_R2R = 9, KERNEL_POW2_FUSED = 10, KERNEL_TRANSPOSE = 11, KERNEL_REAL_MAP = 12, KERNEL_MIXCONV = 13, KERNEL_MIX_FUSED = 14 };
+enum KernelKind : int { KERNEL_GENERIC = 0, KERNEL_POW2_ROW = 1, KERNEL_POW2_COL = 2, KERNEL_R2C_PAIR = 3, KERNEL_MIXED_ROW = 5, KERNEL_OPFFT = 6, KERNEL_POW2_BLUE = 7, KERNEL_POW2_COL_BLUE = 8, KERNEL_POW2_BLUE_R2R = 9, KERNEL_POW2_FUSED = 10, KERNEL_TRANSPOSE = 11, KERNEL_REAL_MAP = 12, KERNEL_MIXCONV = 13, KERNEL_MIX_FUSED = 14, KERNEL_POW2_CONV_ROW = 15 };
 
 struct HostDim {
 	uint64_t count;
@@ -95,6 +95,10 @@ int build_direction_plan(const TransformDesc& d, DirectionPlan& out);
 // d.batch = numberBatches (NOT folded with the coordinates); returns 3002 when no such pass exists for the shape (the caller keeps separate passes)
 struct ConvAxisDesc { uint32_t matrix = 1, coordinates = 1, symmetric = 0, conjugate = 0; double scale = 1.0; uint64_t kernelSystems = 1; };
 int build_conv_axis_plan(const TransformDesc& d, const ConvAxisDesc& c, DirectionPlan& out);
+// One-launch convolution of a ONE-dimensional plan (unit-stride power-of-two rows, pow2_conv_row_kernel in kernel_pow2_conv.h): forward transform, product with
+// the row's kernel spectrum, inverse transform, in registers.  matrix <= 1 only; d.batch = numberBatches; d.kind 1: two real rows per complex transform.
+// Returns 3002 when no instance serves the shape (the caller keeps the three separate launches)
+int build_conv_row_plan(const TransformDesc& d, const ConvAxisDesc& c, DirectionPlan& out);
 
 // launchers (kernels.hip)
 struct LaunchBuffers {
@@ -117,6 +121,7 @@ int execute_direction(const DirectionPlan& plan, const LaunchBuffers& bufs, cons
 int launch_pow2(const PassPlan& pp, const PassParams& prm, hipStream_t stream);
 int launch_pow2_blue(const PassPlan& pp, const PassParams& prm, hipStream_t stream);
 int launch_pow2_col_blue(const PassPlan& pp, const PassParams& prm, hipStream_t stream);
+int launch_pow2_conv_row(const PassPlan& pp, const PassParams& prm, hipStream_t stream);
 // want: the registered shape asked for (Switches, 0 = what ships; an index the size does not have = 0)
 bool pow2_row_lookup(uint32_t log2n, bool dp, int want, int* variant, int bits[4], int* fpw, int* threads, bool padded = false); // padded: only kernels with zero-padding masks
 bool pow2_col_lookup(uint32_t log2n, bool dp, int want, int* variant, int bits[4], int* tc, int* threads);
@@ -124,6 +129,7 @@ bool pow2_col_blue_lookup(uint32_t log2l, bool dp, int mode, int* variant, int b
 bool pow2_blue_r2r_lookup(uint32_t log2m, bool dp, uint32_t pre, int* variant, int bits[4], int* fpw, int* threads); // Bluestein-wrapped DCT/DST/R2C
 int launch_pow2_blue_r2r(const PassPlan& pp, const PassParams& prm, hipStream_t stream);
 bool pow2_blue_lookup(uint32_t log2m, bool dp, int want, int* variant, int bits[4], int* fpw, int* threads); // fused Bluestein on padded length 2^log2m
+bool pow2_conv_row_lookup(uint32_t log2n, bool dp, bool real, int* variant, int bits[4], int* fpw, int* threads); // one-launch 1-D convolution rows (real: pairs of real rows)
 // fused Four-Step of 2^log2n = 2^la * 2^lb (kernels_fused.hip)
 bool pow2_fused_lookup(uint32_t log2n, bool dp, int mode, int want, int* variant, int* la, int* lb, int bitsA[4], int bitsB[4], int* tca, int* tcb, int* threads, int* wgPerCu);
 int launch_pow2_fused(const PassPlan& pp, const FusedParams& prm, hipStream_t stream);

@@ -28,6 +28,8 @@ int launch_pass(const PassPlan& pp, const PassParams& prm, hipStream_t stream) {
 		return launch_pow2_blue(pp, prm, stream);
 	case KERNEL_POW2_COL_BLUE:
 		return launch_pow2_col_blue(pp, prm, stream);
+	case KERNEL_POW2_CONV_ROW:
+		return launch_pow2_conv_row(pp, prm, stream);
 	case KERNEL_TRANSPOSE:
 		return launch_transpose(pp, prm, stream);
 	case KERNEL_REAL_MAP:

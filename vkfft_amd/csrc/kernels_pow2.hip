@@ -3,6 +3,7 @@
 #include "engine.h"
 #include "kernel_pow2.h"
 #include "kernel_pow2_pk.h"
+#include "kernel_pow2_conv.h"
 #include <cstdio>
 #include <cstdlib>
 
@@ -137,6 +138,36 @@ static const Pow2Variant kPow2BlueVariants[] = {
 };
 constexpr int kNumPow2BlueVariants = (int)(sizeof(kPow2BlueVariants) / sizeof(kPow2BlueVariants[0]));
 
+// one-launch 1-D convolution rows (kernel_pow2_conv.h): one entry per (log2 N, dp, real), the shapes of the fused Bluestein rows above — without the 1024-thread
+// shape of 16384 points.  real: the instance that takes pairs of real rows
+template <typename T, typename SCH, int FPW, bool REAL> void pow2_conv_row_launch(const PassParams& prm, dim3 grid, hipStream_t s) {
+	constexpr int threads = ((1 << SCH::LOGN) >> SCH::LOGE) * FPW;
+	const unsigned resident = pow2_num_cus() * 8u; // persistent: the workgroups stride over the row tiles
+	hipLaunchKernelGGL((pow2_conv_row_kernel<T, SCH, FPW, REAL>), dim3(grid.x < resident ? grid.x : resident), dim3(threads), 0, s, prm);
+}
+struct Pow2ConvRowVariant { Pow2Variant v; bool real; };
+#define VKFFT_P2CR1(T, dp, b0, b1, b2, b3, fpw, real) \
+	{ { (b0) + (b1) + (b2) + (b3), dp, {b0, b1, b2, b3}, fpw, (((1 << ((b0) + (b1) + (b2) + (b3))) >> Pow2Sched<b0, b1, b2, b3>::LOGE) * (fpw)), &pow2_conv_row_launch<T, Pow2Sched<b0, b1, b2, b3>, fpw, real> }, real }
+#define VKFFT_P2CR(T, dp, b0, b1, b2, b3, fpw) VKFFT_P2CR1(T, dp, b0, b1, b2, b3, fpw, false), VKFFT_P2CR1(T, dp, b0, b1, b2, b3, fpw, true)
+static const Pow2ConvRowVariant kPow2ConvRowVariants[] = {
+	VKFFT_P2CR(float, false, 3, 3, 0, 0, 32),
+	VKFFT_P2CR(float, false, 4, 3, 0, 0, 16),
+	VKFFT_P2CR(float, false, 4, 4, 0, 0, 16),
+	VKFFT_P2CR(float, false, 4, 3, 2, 0, 8),
+	VKFFT_P2CR(float, false, 4, 3, 3, 0, 4),
+	VKFFT_P2CR(float, false, 4, 4, 3, 0, 2),
+	VKFFT_P2CR(float, false, 4, 4, 4, 0, 1),
+	VKFFT_P2CR(float, false, 4, 3, 3, 3, 1),
+	VKFFT_P2CR(double, true, 3, 3, 0, 0, 32),
+	VKFFT_P2CR(double, true, 3, 2, 2, 0, 16),
+	VKFFT_P2CR(double, true, 3, 3, 2, 0, 8),
+	VKFFT_P2CR(double, true, 3, 3, 3, 0, 4),
+	VKFFT_P2CR(double, true, 3, 3, 2, 2, 2),
+	VKFFT_P2CR(double, true, 3, 3, 3, 2, 1),
+	VKFFT_P2CR(double, true, 3, 3, 3, 3, 1),
+};
+constexpr int kNumPow2ConvRowVariants = (int)(sizeof(kPow2ConvRowVariants) / sizeof(kPow2ConvRowVariants[0]));
+
 // multi-pass Bluestein column kernels: one entry per (log2 L, dp, mode); Pow2Variant::fpw holds the tile width
 template <typename T, typename SCH, int TC, int MODE> void pow2_col_blue_launch(const PassParams& prm, dim3 grid, hipStream_t s) {
 	constexpr int threads = ((1 << SCH::LOGN) >> SCH::LOGE) * TC;
@@ -180,6 +211,13 @@ int launch_pow2_blue(const PassPlan& pp, const PassParams& prm, hipStream_t stre
 	return hipGetLastError() == hipSuccess ? 0 : 4039;
 }
 
+int launch_pow2_conv_row(const PassPlan& pp, const PassParams& prm, hipStream_t stream) {
+	if (prm.tilesPerG0 == 0) return 0;
+	if (pp.variant < 0 || pp.variant >= kNumPow2ConvRowVariants) return 4039;
+	kPow2ConvRowVariants[pp.variant].v.launch(prm, dim3(prm.tilesPerG0), stream);
+	return hipGetLastError() == hipSuccess ? 0 : 4039;
+}
+
 const char* pow2_row_kernel_name(int variant) {
 	if (variant < 0 || variant >= kNumPow2Variants || !kPow2Variants[variant].name) return "pow2_row_kernel";
 	return kPow2Variants[variant].name;
@@ -217,6 +255,17 @@ bool pow2_col_blue_lookup(uint32_t log2l, bool dp, int mode, int* variant, int b
 		*variant = i;
 		for (int k = 0; k < 4; k++) bits[k] = e.v.bits[k];
 		*tc = e.v.fpw; *threads = e.v.threads;
+		return true;
+	}
+	return false;
+}
+bool pow2_conv_row_lookup(uint32_t log2n, bool dp, bool real, int* variant, int bits[4], int* fpw, int* threads) {
+	for (int i = 0; i < kNumPow2ConvRowVariants; i++) {
+		const Pow2ConvRowVariant& e = kPow2ConvRowVariants[i];
+		if (e.v.log2n != (int)log2n || e.v.dp != dp || e.real != real) continue;
+		*variant = i;
+		for (int k = 0; k < 4; k++) bits[k] = e.v.bits[k];
+		*fpw = e.v.fpw; *threads = e.v.threads;
 		return true;
 	}
 	return false;

@@ -2543,6 +2543,49 @@ int build_conv_axis_plan(const TransformDesc& d, const ConvAxisDesc& c, Directio
 	return 0;
 }
 
+// ---- one-launch convolution of a one-dimensional plan -----------------------------------------------------------
+// Unit-stride power-of-two rows with an instance of pow2_conv_row_kernel (kernel_pow2_conv.h): rows b * cf + v of the dense in-place layout, every one
+// multiplied with kernel system v.  C2C: one row per slot; R2C: a slot is the pair of real rows (2 q cf + v, (2 q + 1) cf + v).
+int build_conv_row_plan(const TransformDesc& d, const ConvAxisDesc& c, DirectionPlan& out) {
+	out = DirectionPlan();
+	Arena ar(out.arena);
+	if (d.fftDim != 1 || d.kind > 1 || d.omit[0] || d.padFrequency || d.disableFastKernels || d.inFormatted || d.outFormatted) return 3002;
+	const uint64_t N = d.size[0];
+	if (N < 2 || (N & (N - 1)) != 0 || c.matrix > 1 || c.coordinates < 1) return 3002;
+	const bool dp = d.dp, real = d.kind == 1;
+	if (real && c.conjugate != 0) return 3002; // (conj of one operand is not linear over the a + i b pairing)
+	if (c.conjugate > 2) return 3002;
+	int variant, bits[4], fpw, thr;
+	if (!pow2_conv_row_lookup(ilog2(N), dp, real, &variant, bits, &fpw, &thr)) return 3002;
+	const uint64_t es = dp ? 16 : 8, cf = c.coordinates;
+	const uint64_t pitch = real ? N + 2 : N, kerSys = real ? N / 2 + 1 : N; // reals resp. complex elements per data row; complex elements per kernel system
+	if (d.bufStride[0] != kerSys) return 3002; // dense rows only
+	const uint64_t rows = d.batch * cf, slots = real ? ((d.batch + 1) / 2) * cf : rows;
+	if (rows == 0 || rows >= (1ull << 31) || cf >= (1ull << 20)) return 3002;
+	// 32-bit lane offsets: the rows of a tile (REAL: FPW slots reach over up to 2 * FPW + 2 * cf rows) and every kernel system lie within one buffer resource
+	if ((2 * (uint64_t)fpw + 2 * cf + 2) * pitch * es >= kSpanLimit || (cf + 1) * kerSys * es >= kSpanLimit) return 3002;
+	const uint64_t tiles = (slots + (uint64_t)fpw - 1) / (uint64_t)fpw;
+	if (tiles > 0x7fffffffull) return 3002;
+	PassPlan pp; memset(&pp.prm, 0, sizeof(pp.prm));
+	PassParams& q = pp.prm;
+	q.L = (uint32_t)N; q.inStrideJ = q.outStrideJ = 1;
+	q.dim[0] = {(uint32_t)slots, (int64_t)pitch, (int64_t)pitch};
+	q.dim[1] = {1, 0, 0}; q.dim[2] = {1, 0, 0};
+	q.T = (uint32_t)fpw; q.tilesPerG0 = (uint32_t)tiles;
+	q.convM = 1; q.convCf = (uint32_t)cf; q.convConj = c.conjugate; q.convKerSysStride = (int64_t)kerSys;
+	q.opN = (uint32_t)rows; q.pairRows = real ? 1u : 0u;
+	q.scale = c.scale;
+	if (d.padR[0] > N) return 3002;
+	if (d.padR[0] > d.padL[0]) { q.padInL = q.padOutL = (uint32_t)d.padL[0]; q.padInN = q.padOutN = (uint32_t)(d.padR[0] - d.padL[0]); }
+	pp.lutOff = build_pow2_stage_lut(ar, bits, dp);
+	pp.kernel = KERNEL_POW2_CONV_ROW; pp.variant = variant; pp.threads = (uint32_t)thr; pp.dp = dp; pp.auxIsKernel = true;
+	pp.inRole = pp.outRole = ROLE_BUFFER; pp.inElemBytes = pp.outElemBytes = (int)(real ? es / 2 : es);
+	pp.label = "convolution";
+	out.passes.push_back(pp);
+	out.uploadsPerAxis[0] = 1;
+	return 0;
+}
+
 // ---- top level ----------------------------------------------------------------------------------------
 int build_direction_plan(const TransformDesc& d, DirectionPlan& out) {
 	out = DirectionPlan();
