@@ -5,8 +5,9 @@ CSRC := vkfft_amd/csrc
 LIBDIR := vkfft_amd/lib
 # --offload-compress: the gfx950 code objects are stored zstd-compressed in the library (165 MB -> a third) and unpacked by the HIP runtime when the module loads
 CXXFLAGS := -O3 -std=c++17 -fPIC -fvisibility=hidden -Iinclude -I$(CSRC) -Wno-unused-result --offload-compress
-OBJS := build/obj/api.o build/obj/planner.o build/obj/kernels.o build/obj/kernels_pow2.o build/obj/kernels_blue_r2r.o build/obj/kernels_fused.o build/obj/kernels_mixfused.o build/obj/kernels_aux.o build/obj/kernels_mixed_0.o build/obj/kernels_mixed_1.o build/obj/kernels_mixed_2.o build/obj/kernels_mixed_3.o build/obj/kernels_mixed_4.o build/obj/kernels_mixed_5.o build/obj/kernels_mixed_6.o build/obj/kernels_mixed_7.o build/obj/kernels_mixed_8.o build/obj/kernels_mixed_9.o build/obj/kernels_mixed_10.o build/obj/kernels_mixed_11.o build/obj/kernels_mixed_12.o build/obj/kernels_mixed_13.o build/obj/kernels_mixed_14.o build/obj/kernels_mixed_15.o build/obj/kernels_mixed_16.o build/obj/kernels_mixed_17.o build/obj/kernels_mixed_18.o build/obj/kernels_mixed_19.o \
-        build/obj/kernels_mixconv_0.o build/obj/kernels_mixconv_1.o build/obj/kernels_mixconv_2.o build/obj/kernels_mixconv_3.o build/obj/kernels_mixconv_4.o build/obj/kernels_mixconv_5.o \
+# (the parts of the mixed-radix and cyclic-convolution registries: the lists VKFFT_MIXED_PARTS / VKFFT_MIXCONV_PARTS of kernels.hip)
+OBJS := $(foreach u,api planner kernels kernels_pow2 kernels_blue_r2r kernels_fused kernels_mixfused kernels_aux,build/obj/$(u).o) \
+        $(foreach i,0 1 2 3 4 5 6 7 8 9 10 11 12 13 14 15 16 17 18 19,build/obj/kernels_mixed_$(i).o) $(foreach i,0 1 2 3 4 5,build/obj/kernels_mixconv_$(i).o) \
         $(foreach t,f32_row f32_col f64_row f64_col,build/obj/kernels_opfft_$(t)_0.o build/obj/kernels_opfft_$(t)_1.o) build/obj/kernels_opfft_f32_col_2.o
 # the translation units that take longest to compile (12 minutes each for kernels_mixed_0 ... 5, 4-6 for the others; the rest 2 minutes or less), named first among the
 # library's prerequisites so that a parallel make starts them first and no core waits for one of them at the end; the link line keeps the order of OBJS

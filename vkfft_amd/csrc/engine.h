@@ -14,6 +14,15 @@ namespace vkfft_mi355x {
 // ROLE_TEMP2: a second scratch region behind ROLE_TEMP in the same allocation, for plans that wrap an inner plan which uses ROLE_TEMP itself
 enum BufRole : int { ROLE_BUFFER = 0, ROLE_TEMP = 1, ROLE_INPUT = 2, ROLE_OUTPUT = 3, ROLE_TEMP2 = 4 };
 enum KernelKind : int { KERNEL_GENERIC = 0, KERNEL_POW2_ROW = 1, KERNEL_POW2_COL = 2, KERNEL_R2C_PAIR = 3, KERNEL_MIXED_ROW = 5, KERNEL_OPFFT = 6, KERNEL_POW2_BLUE = 7, KERNEL_POW2_COL_BLUE = 8, KERNEL_POW2_BLUE_R2R = 9, KERNEL_POW2_FUSED = 10, KERNEL_TRANSPOSE = 11, KERNEL_REAL_MAP = 12, KERNEL_MIXCONV = 13, KERNEL_MIX_FUSED = 14, KERNEL_POW2_CONV_ROW = 15 };
+// the names of a kind: as the print-plan lines show it, and its __global__ function (vkfftMI355XDescribePlan); 4 is no kind
+struct KernelKindName { const char* brief; const char* global; };
+inline constexpr KernelKindName kKernelKindNames[] = {
+	{"generic", "generic_pass_kernel"}, {"pow2_row", "pow2_row_kernel"}, {"pow2_col", "pow2_col_kernel"}, {"r2c_pair", "r2c_even_pair_kernel"}, {"?", "?"}, {"mixed_row", "mixed_row_kernel"},
+	{"opfft", "opfft_kernel"}, {"pow2_blue", "pow2_blue_kernel"}, {"pow2_col_blue", "pow2_col_blue_kernel"}, {"pow2_blue_r2r", "pow2_blue_r2r_kernel"}, {"pow2_fused", "pow2_fused_kernel"},
+	{"transpose", "transpose_kernel"}, {"real_map", "real_map_kernel"}, {"mixconv", "mixconv_kernel"}, {"mix_fused", "mix_fused_kernel"}, {"pow2_conv_row", "pow2_conv_row_kernel"}};
+constexpr int kNumKernelKinds = (int)(sizeof(kKernelKindNames) / sizeof(kKernelKindNames[0]));
+static_assert(kNumKernelKinds == KERNEL_POW2_CONV_ROW + 1, "one name per KernelKind, the last enumerator included");
+inline const KernelKindName& kernel_kind_name(int kind) { return kKernelKindNames[kind >= 0 && kind < kNumKernelKinds ? kind : 4]; }
 
 struct HostDim {
 	uint64_t count;
@@ -117,39 +126,59 @@ struct StreamSet {
 // sweep: the application's zig-zag state: every launch walks the buffer opposite to the previous one; nullptr = always front to back
 int execute_direction(const DirectionPlan& plan, const LaunchBuffers& bufs, const StreamSet& streams, uint32_t* sweep = nullptr);
 
-// fast-kernel registry queries used by the planner
+// ---- fast-kernel registries: what a look-up found, the look-ups, the launchers -------------------------------------
+// sched: the stages of the transform, log2 of each radix for the power-of-two families, the radices themselves for the mixed ones (0 / 1 behind the last stage)
+struct KernelShape {
+	int variant = -1;   // index into the family's table; -1: no instance
+	int sched[5] = {0, 0, 0, 0, 0};
+	int perWg = 0;      // rows (unit-stride families) or columns (strided ones) per workgroup
+	int threads = 0;
+	uint64_t len = 0;   // cyclic-convolution family only: the transform length
+	explicit operator bool() const { return variant >= 0; }
+};
+// a fused Four-Step instance: two factors, a schedule each.  n0, n1: the factors (mix_fused_lookup) or their log2 (pow2_fused_lookup)
+struct FusedShape {
+	int variant = -1, n0 = 0, n1 = 0, radA[5] = {0, 0, 0, 0, 0}, radB[5] = {0, 0, 0, 0, 0}, tca = 0, tcb = 0, thr = 0, wgPerCu = 0;
+	explicit operator bool() const { return variant >= 0; }
+};
+// the tail every launcher of a PassParams kernel shares (kernels.hip): nothing to do for an empty grid; 4039 for a grid beyond 31 bits, for fn == nullptr (the
+// launcher found no such instance) and for a launch that the runtime refused
+typedef void (*PassLaunchFn)(const PassParams&, dim3, hipStream_t);
+int launch_on_grid(uint64_t grid64, PassLaunchFn fn, const PassParams& prm, hipStream_t stream);
 int launch_pow2(const PassPlan& pp, const PassParams& prm, hipStream_t stream);
 int launch_pow2_blue(const PassPlan& pp, const PassParams& prm, hipStream_t stream);
 int launch_pow2_col_blue(const PassPlan& pp, const PassParams& prm, hipStream_t stream);
 int launch_pow2_conv_row(const PassPlan& pp, const PassParams& prm, hipStream_t stream);
 // want: the registered shape asked for (Switches, 0 = what ships; an index the size does not have = 0)
-bool pow2_row_lookup(uint32_t log2n, bool dp, int want, int* variant, int bits[4], int* fpw, int* threads, bool padded = false); // padded: only kernels with zero-padding masks
-bool pow2_col_lookup(uint32_t log2n, bool dp, int want, int* variant, int bits[4], int* tc, int* threads);
-bool pow2_col_blue_lookup(uint32_t log2l, bool dp, int mode, int* variant, int bits[4], int* tc, int* threads); // multi-pass Bluestein passes 1..3
-bool pow2_blue_r2r_lookup(uint32_t log2m, bool dp, uint32_t pre, int* variant, int bits[4], int* fpw, int* threads); // Bluestein-wrapped DCT/DST/R2C
+KernelShape pow2_row_lookup(uint32_t log2n, bool dp, int want, bool padded = false); // padded: only kernels with zero-padding masks
+KernelShape pow2_col_lookup(uint32_t log2n, bool dp, int want);
+KernelShape pow2_col_blue_lookup(uint32_t log2l, bool dp, int mode); // multi-pass Bluestein passes 1..3
+KernelShape pow2_blue_r2r_lookup(uint32_t log2m, bool dp, uint32_t pre); // Bluestein-wrapped DCT/DST/R2C
 int launch_pow2_blue_r2r(const PassPlan& pp, const PassParams& prm, hipStream_t stream);
-bool pow2_blue_lookup(uint32_t log2m, bool dp, int want, int* variant, int bits[4], int* fpw, int* threads); // fused Bluestein on padded length 2^log2m
+KernelShape pow2_blue_lookup(uint32_t log2m, bool dp, int want); // fused Bluestein on padded length 2^log2m
 bool pow2_conv_row_lookup(uint32_t log2n, bool dp, bool real, int* variant, int bits[4], int* fpw, int* threads); // one-launch 1-D convolution rows (real: pairs of real rows)
-// fused Four-Step of 2^log2n = 2^la * 2^lb (kernels_fused.hip)
-bool pow2_fused_lookup(uint32_t log2n, bool dp, int mode, int want, int* variant, int* la, int* lb, int bitsA[4], int bitsB[4], int* tca, int* tcb, int* threads, int* wgPerCu);
+// fused Four-Step of 2^log2n = 2^n0 * 2^n1 (kernels_fused.hip)
+FusedShape pow2_fused_lookup(uint32_t log2n, bool dp, int mode, int want);
 int launch_pow2_fused(const PassPlan& pp, const FusedParams& prm, hipStream_t stream);
 // the __global__ function behind a registry entry (vkfftMI355XDescribePlan: bench labels, rocprofv3 kernel names)
 const char* pow2_fused_kernel_name(int variant);
 // fused Four-Step of a non-power-of-two N = n0 * n1 (kernels_mixfused.hip, kernel_mix_fused.h)
-bool mix_fused_lookup(uint64_t n, bool dp, int want, int* variant, int* n0, int* n1, int radA[5], int radB[5], int* tca, int* tcb, int* threads, int* wgPerCu);
+FusedShape mix_fused_lookup(uint64_t n, bool dp, int want);
 int launch_mix_fused(const PassPlan& pp, const FusedParams& prm, hipStream_t stream);
 const char* pow2_row_kernel_name(int variant);
-bool mixed_row_lookup(uint64_t n, bool dp, int* variant, int rad[5], int* fpw, int* threads);
+KernelShape mixed_row_lookup(uint64_t n, bool dp);
 int mixed_row_ops_fpw(int variant); // rows per workgroup of that variant's form between the maps of a real transform
 int launch_mixed(const PassPlan& pp, const PassParams& prm, hipStream_t stream);
 // one-kernel cyclic convolution (kernel_mixconv.h), unit-stride rows or (col) tiles of neighbouring columns of a strided axis.  rader: the instance of prime p (transform length p - 1); otherwise the Bluestein instance with
-// the smallest padded length >= minLen.  *len = transform length
-bool mixconv_lookup(bool rader, bool col, uint64_t pOrMinLen, bool dp, int* variant, uint64_t* len, int rad[5], int* fpw, int* threads);
+// the smallest padded length >= minLen.  KernelShape::len = transform length
+KernelShape mixconv_lookup(bool rader, bool col, uint64_t pOrMinLen, bool dp);
 int launch_mixconv(const PassPlan& pp, const PassParams& prm, hipStream_t stream);
 bool mixrad_available(int variant); // the Rader row instance also exists as a stage of composite lengths (kernel_mixrad.h)
-bool mixrad_geom(int variant, int* sp, int* lutn, int* groups, int* groupsDense); // ... its buffer pitch (elements), stage-twiddle count and thread groups of the wave-aligned layout (0: not offered)
+// ... its buffer pitch (elements), stage-twiddle count and thread groups of the wave-aligned layout (0: not offered); ok: mixrad_available(variant)
+struct MixradShape { bool ok = false; int sp = 0, lutn = 0, groups = 0, groupsDense = 0; };
+MixradShape mixrad_geom(int variant);
 // op-FFT family (kernel_opfft.h): pre/post are the DCT member of their family (DST variants share the instance)
-bool opfft_lookup(uint64_t n, bool dp, bool col, bool trans, uint32_t pre, uint32_t post, int* variant, int rad[5], int* fpw, int* threads); // trans: column tile in, transposed (per-column contiguous) store out
+KernelShape opfft_lookup(uint64_t n, bool dp, bool col, bool trans, uint32_t pre, uint32_t post); // trans: column tile in, transposed (per-column contiguous) store out
 int launch_opfft(const PassPlan& pp, const PassParams& prm, hipStream_t stream);
 
 // convolution product and zero padding (kernels_aux.hip)

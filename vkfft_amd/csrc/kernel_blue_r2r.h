@@ -158,7 +158,7 @@ int launch_pow2_blue_r2r(const PassPlan& pp, const PassParams& prm, hipStream_t 
 	return hipGetLastError() == hipSuccess ? 0 : 4039;
 }
 
-bool pow2_blue_r2r_lookup(uint32_t log2m, bool dp, uint32_t pre, int* variant, int bits[4], int* fpw, int* threads) {
+KernelShape pow2_blue_r2r_lookup(uint32_t log2m, bool dp, uint32_t pre) {
 	switch (pre) { // DST members run on the DCT instance of their family
 	case OP_DST2_PRE: pre = OP_DCT2_PRE; break;
 	case OP_DST3_PRE: pre = OP_DCT3_PRE; break;
@@ -167,13 +167,9 @@ bool pow2_blue_r2r_lookup(uint32_t log2m, bool dp, uint32_t pre, int* variant, i
 	}
 	for (int i = 0; i < kNumPow2BlueR2rVariants; i++) {
 		const Pow2BlueR2rVariant& e = kPow2BlueR2rVariants[i];
-		if (e.v.log2n != (int)log2m || e.v.dp != dp || (uint32_t)e.pre != pre) continue;
-		*variant = i;
-		for (int k = 0; k < 4; k++) bits[k] = e.v.bits[k];
-		*fpw = e.v.fpw; *threads = e.v.threads;
-		return true;
+		if (e.v.log2n == (int)log2m && e.v.dp == dp && (uint32_t)e.pre == pre) return pow2_shape(e.v, i);
 	}
-	return false;
+	return {};
 }
 
 } // namespace vkfft_mi355x

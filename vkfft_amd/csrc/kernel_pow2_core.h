@@ -195,5 +195,11 @@ struct Pow2Variant {
 	const char* name = nullptr; // the __global__ function behind the entry when it is not the family's first (vkfftMI355XDescribePlan, bench labels)
 	bool noPadMasks = false;    // the kernel has no zero-padding masks: a padded pass takes the next entry of its size
 };
+inline KernelShape pow2_shape(const Pow2Variant& v, int index) { // what the look-ups answer for entry `index` of a table of these
+	KernelShape k;
+	k.variant = index; k.perWg = v.fpw; k.threads = v.threads;
+	for (int i = 0; i < 4; i++) k.sched[i] = v.bits[i];
+	return k;
+}
 
 } // namespace vkfft_mi355x

@@ -67,46 +67,43 @@ int launch_pass(const PassPlan& pp, const PassParams& prm, hipStream_t stream) {
 	return hipGetLastError() == hipSuccess ? 0 : 4039;
 }
 
-// ---- mixed-radix registry: six table parts, one translation unit each (kernels_mixed_*.hip) --------------------
-constexpr int kMixedParts = 20; // (parts 6-8: tools/gen_long_rows_table.py — the long rows; the 7-smooth lengths of 4097 ... 8192 points outside the first six tables)
-const MixedVariant* mixed_table_0(int*);
-const MixedVariant* mixed_table_1(int*);
-const MixedVariant* mixed_table_2(int*);
-const MixedVariant* mixed_table_3(int*);
-const MixedVariant* mixed_table_4(int*);
-const MixedVariant* mixed_table_5(int*);
-const MixedVariant* mixed_table_6(int*);
-const MixedVariant* mixed_table_7(int*);
-const MixedVariant* mixed_table_8(int*);
-const MixedVariant* mixed_table_9(int*);
-const MixedVariant* mixed_table_10(int*);
-const MixedVariant* mixed_table_11(int*);
-const MixedVariant* mixed_table_12(int*);
-const MixedVariant* mixed_table_13(int*);
-const MixedVariant* mixed_table_14(int*);
-const MixedVariant* mixed_table_15(int*);
-const MixedVariant* mixed_table_16(int*);
-const MixedVariant* mixed_table_17(int*);
-const MixedVariant* mixed_table_18(int*);
-const MixedVariant* mixed_table_19(int*);
-static const MixedVariant* mixed_part(int part, int* count) {
-	typedef const MixedVariant* (*Fn)(int*);
-	static const Fn fns[kMixedParts] = {&mixed_table_0, &mixed_table_1, &mixed_table_2, &mixed_table_3, &mixed_table_4, &mixed_table_5, &mixed_table_6, &mixed_table_7, &mixed_table_8, &mixed_table_9, &mixed_table_10, &mixed_table_11, &mixed_table_12, &mixed_table_13, &mixed_table_14, &mixed_table_15, &mixed_table_16, &mixed_table_17, &mixed_table_18, &mixed_table_19};
-	return fns[part % kMixedParts](count);
+int launch_on_grid(uint64_t grid64, PassLaunchFn fn, const PassParams& prm, hipStream_t stream) {
+	if (grid64 == 0) return 0;
+	if (grid64 > 0x7fffffffull || !fn) return 4039;
+	fn(prm, dim3((uint32_t)grid64), stream);
+	return hipGetLastError() == hipSuccess ? 0 : 4039;
 }
-bool mixed_row_lookup(uint64_t n, bool dp, int* variant, int rad[5], int* fpw, int* threads) {
+
+// A registry in parts, one translation unit each: PARTS(X) lists the suffixes of `<family>_table_<suffix>(int* count)`; this declares them and defines
+// <family>_part(part, &count) and the part count
+#define VKFFT_PART_DECL(Variant, family, t) const Variant* family##_table_##t(int*);
+#define VKFFT_PART_REF(Variant, family, t) &family##_table_##t,
+#define VKFFT_REGISTRY_PARTS(Variant, family, kParts, PARTS) \
+	PARTS(VKFFT_PART_DECL, Variant, family) \
+	typedef const Variant* (*family##_part_fn)(int*); \
+	static const family##_part_fn family##_part_fns[] = { PARTS(VKFFT_PART_REF, Variant, family) }; \
+	constexpr int kParts = (int)(sizeof(family##_part_fns) / sizeof(family##_part_fns[0]));
+
+// ---- mixed-radix registry: twenty table parts (kernels_mixed_*.hip).  Parts 6-19: tools/gen_long_rows_table.py — the long rows; the 7-smooth lengths of 4097 ... 8192 points outside the first six tables
+#define VKFFT_MIXED_PARTS(X, V, f) X(V, f, 0) X(V, f, 1) X(V, f, 2) X(V, f, 3) X(V, f, 4) X(V, f, 5) X(V, f, 6) X(V, f, 7) X(V, f, 8) X(V, f, 9) \
+	X(V, f, 10) X(V, f, 11) X(V, f, 12) X(V, f, 13) X(V, f, 14) X(V, f, 15) X(V, f, 16) X(V, f, 17) X(V, f, 18) X(V, f, 19)
+VKFFT_REGISTRY_PARTS(MixedVariant, mixed, kMixedParts, VKFFT_MIXED_PARTS)
+static const MixedVariant* mixed_part(int part, int* count) { // (a negative part — of a variant of -1, no instance — has no entries)
+	return part < 0 ? nullptr : mixed_part_fns[part % kMixedParts](count);
+}
+KernelShape mixed_row_lookup(uint64_t n, bool dp) {
 	for (int part = 0; part < kMixedParts; part++) {
 		int cnt = 0;
 		const MixedVariant* tab = mixed_part(part, &cnt);
 		for (int i = 0; i < cnt; i++) {
 			if ((uint64_t)tab[i].n != n || tab[i].dp != dp) continue;
-			*variant = (part << 16) | i;
-			for (int k = 0; k < 5; k++) rad[k] = tab[i].rad[k];
-			*fpw = tab[i].fpw; *threads = tab[i].tpf * tab[i].fpw;
-			return true;
+			KernelShape k;
+			k.variant = (part << 16) | i; k.perWg = tab[i].fpw; k.threads = tab[i].tpf * tab[i].fpw;
+			for (int r = 0; r < 5; r++) k.sched[r] = tab[i].rad[r];
+			return k;
 		}
 	}
-	return false;
+	return {};
 }
 // rows per workgroup of the variant's form between the maps (kernel_mixed.h mixed_ops_fpw)
 int mixed_row_ops_fpw(int variant) {
@@ -116,33 +113,22 @@ int mixed_row_ops_fpw(int variant) {
 	return (variant < 0 || idx >= cnt) ? 0 : tab[idx].fpwOps;
 }
 int launch_mixed(const PassPlan& pp, const PassParams& prm, hipStream_t stream) {
-	const uint64_t grid64 = (uint64_t)prm.tilesPerG0 * prm.dim[1].count * prm.dim[2].count;
-	if (grid64 == 0) return 0;
 	int cnt = 0;
 	const MixedVariant* tab = mixed_part((pp.variant >> 16) % kMixedParts, &cnt);
 	const int idx = pp.variant & 0xffff;
-	if (grid64 > 0x7fffffffull || pp.variant < 0 || idx >= cnt) return 4039;
-	if (prm.preOp != OP_NONE || prm.postOp != OP_NONE) tab[idx].launchOps(prm, dim3((uint32_t)grid64), stream);
-	else tab[idx].launch(prm, dim3((uint32_t)grid64), stream);
-	return hipGetLastError() == hipSuccess ? 0 : 4039;
+	const bool known = pp.variant >= 0 && idx < cnt, ops = prm.preOp != OP_NONE || prm.postOp != OP_NONE;
+	return launch_on_grid((uint64_t)prm.tilesPerG0 * prm.dim[1].count * prm.dim[2].count, !known ? nullptr : ops ? tab[idx].launchOps : tab[idx].launch, prm, stream);
 }
 
 // ---- one-kernel cyclic convolution registry: six table parts (kernels_mixconv_*.hip) ---------------------------------
-constexpr int kMixConvParts = 6;
-const MixConvVariant* mixconv_table_0(int*);
-const MixConvVariant* mixconv_table_1(int*);
-const MixConvVariant* mixconv_table_2(int*);
-const MixConvVariant* mixconv_table_3(int*);
-const MixConvVariant* mixconv_table_4(int*);
-const MixConvVariant* mixconv_table_5(int*);
+#define VKFFT_MIXCONV_PARTS(X, V, f) X(V, f, 0) X(V, f, 1) X(V, f, 2) X(V, f, 3) X(V, f, 4) X(V, f, 5)
+VKFFT_REGISTRY_PARTS(MixConvVariant, mixconv, kMixConvParts, VKFFT_MIXCONV_PARTS)
 static const MixConvVariant* mixconv_part(int part, int* count) {
-	typedef const MixConvVariant* (*Fn)(int*);
-	static const Fn fns[kMixConvParts] = {&mixconv_table_0, &mixconv_table_1, &mixconv_table_2, &mixconv_table_3, &mixconv_table_4, &mixconv_table_5};
-	return fns[part % kMixConvParts](count);
+	return part < 0 ? nullptr : mixconv_part_fns[part % kMixConvParts](count);
 }
-bool mixconv_lookup(bool rader, bool col, uint64_t pOrMinLen, bool dp, int* variant, uint64_t* len, int rad[5], int* fpw, int* threads) {
+KernelShape mixconv_lookup(bool rader, bool col, uint64_t pOrMinLen, bool dp) {
 	const MixConvVariant* best = nullptr;
-	int bestId = -1;
+	KernelShape k;
 	for (int part = 0; part < kMixConvParts; part++) {
 		int cnt = 0;
 		const MixConvVariant* tab = mixconv_part(part, &cnt);
@@ -151,14 +137,13 @@ bool mixconv_lookup(bool rader, bool col, uint64_t pOrMinLen, bool dp, int* vari
 			if (v.dp != dp || (v.rader != 0) != rader || (v.col != 0) != col) continue;
 			if (rader ? (uint64_t)v.l + 1 != pOrMinLen : (uint64_t)v.l < pOrMinLen) continue;
 			if (best && best->l <= v.l) continue;
-			best = &v; bestId = (part << 16) | i;
+			best = &v; k.variant = (part << 16) | i;
 		}
 	}
-	if (!best) return false;
-	*variant = bestId; *len = (uint64_t)best->l;
-	for (int k = 0; k < 5; k++) rad[k] = best->rad[k];
-	*fpw = best->fpw; *threads = best->tpf * best->fpw;
-	return true;
+	if (!best) return k;
+	k.len = (uint64_t)best->l; k.perWg = best->fpw; k.threads = best->tpf * best->fpw;
+	for (int i = 0; i < 5; i++) k.sched[i] = best->rad[i];
+	return k;
 }
 bool mixrad_available(int variant) {
 	int cnt = 0;
@@ -166,46 +151,38 @@ bool mixrad_available(int variant) {
 	const int idx = variant & 0xffff;
 	return variant >= 0 && idx < cnt && tab[idx].launchRad != nullptr;
 }
-bool mixrad_geom(int variant, int* sp, int* lutn, int* groups, int* groupsDense) {
-	if (!mixrad_available(variant)) return false;
+MixradShape mixrad_geom(int variant) {
+	MixradShape g;
+	if (!mixrad_available(variant)) return g;
 	int cnt = 0;
-	const MixConvVariant* tab = mixconv_part((variant >> 16) % kMixConvParts, &cnt);
-	*sp = tab[variant & 0xffff].radSP; *lutn = tab[variant & 0xffff].radLutN; *groups = tab[variant & 0xffff].radGroups; *groupsDense = tab[variant & 0xffff].radGroupsDense;
-	return true;
+	const MixConvVariant& v = mixconv_part((variant >> 16) % kMixConvParts, &cnt)[variant & 0xffff];
+	g.ok = true; g.sp = v.radSP; g.lutn = v.radLutN; g.groups = v.radGroups; g.groupsDense = v.radGroupsDense;
+	return g;
 }
 int launch_mixconv(const PassPlan& pp, const PassParams& prm, hipStream_t stream) {
-	const uint64_t grid64 = (uint64_t)prm.tilesPerG0 * (prm.colMerge ? 1u : prm.dim[1].count) * prm.dim[2].count;
-	if (grid64 == 0) return 0;
 	int cnt = 0;
 	const MixConvVariant* tab = mixconv_part((pp.variant >> 16) % kMixConvParts, &cnt);
 	const int idx = pp.variant & 0xffff;
-	if (grid64 > 0x7fffffffull || pp.variant < 0 || idx >= cnt) return 4039;
-	if (prm.raderM >= 1) { // the prime as a stage of the composite length raderM * P (kernel_mixrad.h; 1: the prime's own rows)
-		if (!tab[idx].launchRad) return 4039;
-		tab[idx].launchRad(prm, dim3((uint32_t)grid64), stream);
-		return hipGetLastError() == hipSuccess ? 0 : 4039;
-	}
-	if ((prm.preOp != OP_NONE || prm.postOp != OP_NONE) && prm.preOp != OP_BLUESTEIN_PRE) { // (the Bluestein form handles its chirp itself: not the interpreter's maps)
-		if (!tab[idx].launchOps) return 4039;
-		tab[idx].launchOps(prm, dim3((uint32_t)grid64), stream);
-		return hipGetLastError() == hipSuccess ? 0 : 4039;
-	}
-	tab[idx].launch(prm, dim3((uint32_t)grid64), stream);
-	return hipGetLastError() == hipSuccess ? 0 : 4039;
+	const bool known = pp.variant >= 0 && idx < cnt;
+	const bool rad = prm.raderM >= 1; // the prime as a stage of the composite length raderM * P (kernel_mixrad.h; 1: the prime's own rows)
+	const bool ops = (prm.preOp != OP_NONE || prm.postOp != OP_NONE) && prm.preOp != OP_BLUESTEIN_PRE; // (the Bluestein form handles its chirp itself: not the interpreter's maps)
+	const PassLaunchFn fn = !known ? nullptr : rad ? tab[idx].launchRad : ops ? tab[idx].launchOps : tab[idx].launch; // (nullptr where the instance has no such form)
+	return launch_on_grid((uint64_t)prm.tilesPerG0 * (prm.colMerge ? 1u : prm.dim[1].count) * prm.dim[2].count, fn, prm, stream);
 }
 
-// ---- op-FFT registry: eight table parts, one translation unit each (kernels_opfft_*.hip) ---------------------------
-#define VKFFT_OPFFT_PARTS(X) X(f32_row_0) X(f32_row_1) X(f32_col_0) X(f32_col_1) X(f64_row_0) X(f64_row_1) X(f64_col_0) X(f64_col_1) X(f32_col_2) /* part 8: tools/gen_opfft_col_extra.py */
-#define VKFFT_DECL(t) const OpfftVariant* opfft_table_##t(int*);
-VKFFT_OPFFT_PARTS(VKFFT_DECL)
-#undef VKFFT_DECL
+// ---- op-FFT registry: nine table parts, one translation unit each (kernels_opfft_*.hip) ---------------------------
+#define VKFFT_OPFFT_PARTS(X, V, f) X(V, f, f32_row_0) X(V, f, f32_row_1) X(V, f, f32_col_0) X(V, f, f32_col_1) X(V, f, f64_row_0) X(V, f, f64_row_1) X(V, f, f64_col_0) X(V, f, f64_col_1) \
+	X(V, f, f32_col_2) /* part 8: tools/gen_opfft_col_extra.py */
+VKFFT_REGISTRY_PARTS(OpfftVariant, opfft, kOpfftParts, VKFFT_OPFFT_PARTS)
 static const OpfftVariant* opfft_part(int part, int* count) { // part = 2 * ((dp ? 2 : 0) + (col ? 1 : 0)) + half
-	typedef const OpfftVariant* (*Fn)(int*);
-#define VKFFT_REF(t) &opfft_table_##t,
-	static const Fn fns[9] = { VKFFT_OPFFT_PARTS(VKFFT_REF) };
-#undef VKFFT_REF
-	return fns[part >= 0 && part < 9 ? part : 0](count);
+	return opfft_part_fns[part >= 0 && part < kOpfftParts ? part : 0](count);
 }
+#undef VKFFT_REGISTRY_PARTS
+#undef VKFFT_PART_REF
+#undef VKFFT_PART_DECL
+#undef VKFFT_OPFFT_PARTS
+#undef VKFFT_MIXCONV_PARTS
+#undef VKFFT_MIXED_PARTS
 static uint32_t opfft_family(uint32_t op) { // DST members run on the DCT instance of their family
 	switch (op) {
 	case OP_DST2_PRE: return OP_DCT2_PRE; case OP_DST2_POST: return OP_DCT2_POST;
@@ -216,7 +193,7 @@ static uint32_t opfft_family(uint32_t op) { // DST members run on the DCT instan
 	default: return op;
 	}
 }
-bool opfft_lookup(uint64_t n, bool dp, bool col, bool trans, uint32_t pre, uint32_t post, int* variant, int rad[5], int* fpw, int* threads) {
+KernelShape opfft_lookup(uint64_t n, bool dp, bool col, bool trans, uint32_t pre, uint32_t post) {
 	pre = opfft_family(pre); post = opfft_family(post);
 	for (int half = 0; half < ((!dp && col) ? 3 : 2); half++) {
 		const int part = half == 2 ? 8 : 2 * ((dp ? 2 : 0) + (col ? 1 : 0)) + half; // (fp32 column tiles have a third part)
@@ -224,23 +201,19 @@ bool opfft_lookup(uint64_t n, bool dp, bool col, bool trans, uint32_t pre, uint3
 		const OpfftVariant* tab = opfft_part(part, &cnt);
 		for (int i = 0; i < cnt; i++) {
 			if ((uint64_t)tab[i].n != n || (uint32_t)tab[i].pre != pre || (uint32_t)tab[i].post != post || tab[i].trans != trans) continue;
-			*variant = (part << 16) | i;
-			for (int k = 0; k < 5; k++) rad[k] = tab[i].rad[k];
-			*fpw = tab[i].fpw; *threads = tab[i].tpf * tab[i].fpw;
-			return true;
+			KernelShape k;
+			k.variant = (part << 16) | i; k.perWg = tab[i].fpw; k.threads = tab[i].tpf * tab[i].fpw;
+			for (int r = 0; r < 5; r++) k.sched[r] = tab[i].rad[r];
+			return k;
 		}
 	}
-	return false;
+	return {};
 }
 int launch_opfft(const PassPlan& pp, const PassParams& prm, hipStream_t stream) {
-	const uint64_t grid64 = (uint64_t)prm.tilesPerG0 * (prm.colMerge ? 1u : prm.dim[1].count) * prm.dim[2].count;
-	if (grid64 == 0) return 0;
 	int cnt = 0;
 	const OpfftVariant* tab = opfft_part(pp.variant >> 16, &cnt);
 	const int idx = pp.variant & 0xffff;
-	if (grid64 > 0x7fffffffull || pp.variant < 0 || idx >= cnt) return 4039;
-	tab[idx].launch(prm, dim3((uint32_t)grid64), stream);
-	return hipGetLastError() == hipSuccess ? 0 : 4039;
+	return launch_on_grid((uint64_t)prm.tilesPerG0 * (prm.colMerge ? 1u : prm.dim[1].count) * prm.dim[2].count, pp.variant >= 0 && idx < cnt ? tab[idx].launch : nullptr, prm, stream);
 }
 
 static int launch_with_hostloop(const PassPlan& pp, PassParams prm, const StreamSet& ss, uint32_t& rr, size_t level) {

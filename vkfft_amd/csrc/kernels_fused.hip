@@ -111,13 +111,14 @@ static const Pow2FusedVariant kPow2FusedVariants[] = {
 };
 constexpr int kNumPow2FusedVariants = (int)(sizeof(kPow2FusedVariants) / sizeof(kPow2FusedVariants[0]));
 
-bool pow2_fused_lookup(uint32_t log2n, bool dp, int mode, int want, int* variant, int* la, int* lb, int bitsA[4], int bitsB[4], int* tca, int* tcb, int* threads, int* wgPerCu) {
+FusedShape pow2_fused_lookup(uint32_t log2n, bool dp, int mode, int want) {
 	const int found = pick_variant(kNumPow2FusedVariants, want, [&](int i) { const Pow2FusedVariant& v = kPow2FusedVariants[i]; return v.log2n == (int)log2n && v.dp == dp && v.mode == mode ? 1 : 0; });
-	if (found < 0) return false;
+	FusedShape s;
+	if (found < 0) return s;
 	const Pow2FusedVariant& v = kPow2FusedVariants[found];
-	*variant = found; *la = v.la; *lb = v.lb; *tca = v.tca; *tcb = v.tcb; *threads = v.threads; *wgPerCu = v.wgPerCu;
-	for (int k = 0; k < 4; k++) { bitsA[k] = v.bitsA[k]; bitsB[k] = v.bitsB[k]; }
-	return true;
+	s.variant = found; s.n0 = v.la; s.n1 = v.lb; s.tca = v.tca; s.tcb = v.tcb; s.thr = v.threads; s.wgPerCu = v.wgPerCu;
+	for (int k = 0; k < 4; k++) { s.radA[k] = v.bitsA[k]; s.radB[k] = v.bitsB[k]; }
+	return s;
 }
 
 const char* pow2_fused_kernel_name(int variant) {

@@ -59,11 +59,11 @@ static const MixFusedVariant kMixFusedVariants[] = {
 	VKFFT_MXB(8, 8, 4, 4, 128, 8, 8, 8, 4, 4, 128, 8, 4),     // 2^20 = 1024 x 1024
 	VKFFT_MXB(12, 9, 9, 1, 108, 8, 12, 10, 9, 1, 108, 8, 4),  // 1049760 = 972 x 1080
 };
-// mix_fused_lookup(n | kMixFusedBlueQuery, ...) asks for the smallest chirp-z instance of n points or more (its length = *n0 * *n1)
+// mix_fused_lookup(n | kMixFusedBlueQuery, ...) asks for the smallest chirp-z instance of n points or more (its length = n0 * n1)
 constexpr uint64_t kMixFusedBlueQuery = 1ull << 63;
 constexpr int kNumMixFusedVariants = (int)(sizeof(kMixFusedVariants) / sizeof(kMixFusedVariants[0]));
 
-bool mix_fused_lookup(uint64_t n, bool dp, int want, int* variant, int* n0, int* n1, int radA[5], int radB[5], int* tca, int* tcb, int* threads, int* wgPerCu) {
+FusedShape mix_fused_lookup(uint64_t n, bool dp, int want) {
 	int found = -1;
 	if (n & kMixFusedBlueQuery) {
 		const uint64_t minLen = n & ~kMixFusedBlueQuery;
@@ -73,11 +73,12 @@ bool mix_fused_lookup(uint64_t n, bool dp, int want, int* variant, int* n0, int*
 			if (found < 0 || v.n < kMixFusedVariants[found].n) found = i;
 		}
 	} else found = pick_variant(kNumMixFusedVariants, want, [&](int i) { const MixFusedVariant& v = kMixFusedVariants[i]; return v.n == n && v.dp == dp && !v.blue ? 1 : 0; });
-	if (found < 0) return false;
+	FusedShape s;
+	if (found < 0) return s;
 	const MixFusedVariant& v = kMixFusedVariants[found];
-	*variant = found; *n0 = v.n0; *n1 = v.n1; *tca = v.tca; *tcb = v.tcb; *threads = v.threads; *wgPerCu = v.wgPerCu;
-	for (int k = 0; k < 5; k++) { radA[k] = v.radA[k]; radB[k] = v.radB[k]; }
-	return true;
+	s.variant = found; s.n0 = v.n0; s.n1 = v.n1; s.tca = v.tca; s.tcb = v.tcb; s.thr = v.threads; s.wgPerCu = v.wgPerCu;
+	for (int k = 0; k < 5; k++) { s.radA[k] = v.radA[k]; s.radB[k] = v.radB[k]; }
+	return s;
 }
 
 int launch_mix_fused(const PassPlan& pp, const FusedParams& prm, hipStream_t stream) {

@@ -196,19 +196,13 @@ static const Pow2ColBlueVariant kPow2ColBlueVariants[] = {
 constexpr int kNumPow2ColBlueVariants = (int)(sizeof(kPow2ColBlueVariants) / sizeof(kPow2ColBlueVariants[0]));
 
 int launch_pow2_col_blue(const PassPlan& pp, const PassParams& prm, hipStream_t stream) {
-	const uint64_t grid64 = (uint64_t)prm.tilesPerG0 * prm.dim[1].count * prm.dim[2].count;
-	if (grid64 == 0) return 0;
-	if (grid64 > 0x7fffffffull || pp.variant < 0 || pp.variant >= kNumPow2ColBlueVariants) return 4039;
-	kPow2ColBlueVariants[pp.variant].v.launch(prm, dim3((uint32_t)grid64), stream);
-	return hipGetLastError() == hipSuccess ? 0 : 4039;
+	const bool known = pp.variant >= 0 && pp.variant < kNumPow2ColBlueVariants;
+	return launch_on_grid((uint64_t)prm.tilesPerG0 * prm.dim[1].count * prm.dim[2].count, known ? kPow2ColBlueVariants[pp.variant].v.launch : nullptr, prm, stream);
 }
 
 int launch_pow2_blue(const PassPlan& pp, const PassParams& prm, hipStream_t stream) {
-	const uint64_t grid64 = (uint64_t)prm.tilesPerG0 * prm.dim[1].count * prm.dim[2].count;
-	if (grid64 == 0) return 0;
-	if (grid64 > 0x7fffffffull || pp.variant < 0 || pp.variant >= kNumPow2BlueVariants) return 4039;
-	kPow2BlueVariants[pp.variant].launch(prm, dim3((uint32_t)grid64), stream);
-	return hipGetLastError() == hipSuccess ? 0 : 4039;
+	const bool known = pp.variant >= 0 && pp.variant < kNumPow2BlueVariants;
+	return launch_on_grid((uint64_t)prm.tilesPerG0 * prm.dim[1].count * prm.dim[2].count, known ? kPow2BlueVariants[pp.variant].launch : nullptr, prm, stream);
 }
 
 int launch_pow2_conv_row(const PassPlan& pp, const PassParams& prm, hipStream_t stream) {
@@ -224,40 +218,31 @@ const char* pow2_row_kernel_name(int variant) {
 }
 
 int launch_pow2(const PassPlan& pp, const PassParams& prm, hipStream_t stream) {
-	const uint64_t grid64 = (uint64_t)prm.tilesPerG0 * (prm.colMerge ? 1u : prm.dim[1].count) * prm.dim[2].count;
-	if (grid64 == 0) return 0;
 	const bool col = pp.kernel == KERNEL_POW2_COL;
-	if (grid64 > 0x7fffffffull || pp.variant < 0 || pp.variant >= (col ? kNumPow2ColVariants : kNumPow2Variants)) return 4039;
-	(col ? kPow2ColVariants : kPow2Variants)[pp.variant].launch(prm, dim3((uint32_t)grid64), stream);
-	return hipGetLastError() == hipSuccess ? 0 : 4039;
+	const bool known = pp.variant >= 0 && pp.variant < (col ? kNumPow2ColVariants : kNumPow2Variants);
+	return launch_on_grid((uint64_t)prm.tilesPerG0 * (prm.colMerge ? 1u : prm.dim[1].count) * prm.dim[2].count, known ? (col ? kPow2ColVariants : kPow2Variants)[pp.variant].launch : nullptr, prm, stream);
 }
 
-
-static bool pow2_lookup(const Pow2Variant* tab, int ntab, int want, uint32_t log2n, bool dp, int* variant, int bits[4], int* fpw, int* threads, bool padded = false) {
+static KernelShape pow2_lookup(const Pow2Variant* tab, int ntab, int want, uint32_t log2n, bool dp, bool padded = false) {
 	const int found = pick_variant(ntab, want, [&](int i) { return tab[i].log2n != (int)log2n || tab[i].dp != dp ? 0 : padded && tab[i].noPadMasks ? 2 : 1; });
-	if (found < 0) return false;
-	*variant = found;
-	for (int k = 0; k < 4; k++) bits[k] = tab[found].bits[k];
-	*fpw = tab[found].fpw; *threads = tab[found].threads;
-	return true;
+	return found < 0 ? KernelShape{} : pow2_shape(tab[found], found);
 }
-bool pow2_row_lookup(uint32_t log2n, bool dp, int want, int* variant, int bits[4], int* fpw, int* threads, bool padded) {
-	return pow2_lookup(kPow2Variants, kNumPow2Variants, want, log2n, dp, variant, bits, fpw, threads, padded);
+KernelShape pow2_row_lookup(uint32_t log2n, bool dp, int want, bool padded) {
+	return pow2_lookup(kPow2Variants, kNumPow2Variants, want, log2n, dp, padded);
 }
-bool pow2_col_lookup(uint32_t log2n, bool dp, int want, int* variant, int bits[4], int* tc, int* threads) {
-	return pow2_lookup(kPow2ColVariants, kNumPow2ColVariants, want, log2n, dp, variant, bits, tc, threads);
+KernelShape pow2_col_lookup(uint32_t log2n, bool dp, int want) {
+	return pow2_lookup(kPow2ColVariants, kNumPow2ColVariants, want, log2n, dp);
+}
+KernelShape pow2_blue_lookup(uint32_t log2m, bool dp, int want) {
+	return pow2_lookup(kPow2BlueVariants, kNumPow2BlueVariants, want, log2m, dp);
 }
 
-bool pow2_col_blue_lookup(uint32_t log2l, bool dp, int mode, int* variant, int bits[4], int* tc, int* threads) {
+KernelShape pow2_col_blue_lookup(uint32_t log2l, bool dp, int mode) {
 	for (int i = 0; i < kNumPow2ColBlueVariants; i++) {
 		const Pow2ColBlueVariant& e = kPow2ColBlueVariants[i];
-		if (e.v.log2n != (int)log2l || e.v.dp != dp || e.mode != mode) continue;
-		*variant = i;
-		for (int k = 0; k < 4; k++) bits[k] = e.v.bits[k];
-		*tc = e.v.fpw; *threads = e.v.threads;
-		return true;
+		if (e.v.log2n == (int)log2l && e.v.dp == dp && e.mode == mode) return pow2_shape(e.v, i);
 	}
-	return false;
+	return {};
 }
 bool pow2_conv_row_lookup(uint32_t log2n, bool dp, bool real, int* variant, int bits[4], int* fpw, int* threads) {
 	for (int i = 0; i < kNumPow2ConvRowVariants; i++) {
@@ -270,9 +255,5 @@ bool pow2_conv_row_lookup(uint32_t log2n, bool dp, bool real, int* variant, int 
 	}
 	return false;
 }
-bool pow2_blue_lookup(uint32_t log2m, bool dp, int want, int* variant, int bits[4], int* fpw, int* threads) {
-	return pow2_lookup(kPow2BlueVariants, kNumPow2BlueVariants, want, log2m, dp, variant, bits, fpw, threads);
-}
-
 
 } // namespace vkfft_mi355x

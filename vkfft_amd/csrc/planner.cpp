@@ -102,6 +102,18 @@ static void host_fft(std::vector<cld>& a);
 
 // buffer addressing of the fast kernels (32-bit offsets from a tile's base): a tile must span less than 2 GiB on both sides
 constexpr uint64_t kSpanLimit = 0x7FFFFF00ull;
+// elements between consecutive rows of a job of unit-stride rows of N points: the larger pitch of its two sides
+static uint64_t row_pitch(const std::vector<HostDim>& others, uint64_t N) {
+	return others.empty() ? N : (uint64_t)std::max<int64_t>(std::llabs(others[0].inStride), std::llabs(others[0].outStride));
+}
+// a tile of 64 rows stays inside 32-bit offsets.  rowLen, elemBytes: N points of 16 / 8 bytes for complex rows, 2 N reals of 8 / 4 bytes for the rows of a real transform
+static bool tile64_in_span(uint64_t pitch, uint64_t rowLen, uint64_t elemBytes) { return (pitch * 64 + rowLen) * elemBytes < kSpanLimit; }
+// padded length of a Bluestein transform of N points on a power-of-two kernel: the first power of two from `floor` on that holds 2 N - 1 points
+static uint64_t blue_pow2_len(uint64_t N, uint64_t floor) {
+	uint64_t M = floor;
+	while (M < 2 * N - 1) M *= 2;
+	return M;
+}
 
 struct PassBuild {
 	const Switches& sw; // the plan's snapshot of the environment (TransformDesc::sw)
@@ -206,12 +218,17 @@ static bool mixrad_choose(const Switches& sw, uint64_t L, bool dp, bool ops, Mix
 		A = 1;
 	} else if (M == P) A = 0; // P * P: the column transform is the prime's own convolution (kernel_mixrad.h, 2b)
 	else if (!mixrad_split((uint32_t)M, A, B)) return false;
-	uint64_t len; int sp = 0, lutn = 0, groups = 0, gd = 0;
-	if (!mixconv_lookup(true, false, P, dp, &c.variant, &len, c.rad, &c.fpw, &c.threads) || !mixrad_geom(c.variant, &sp, &lutn, &groups, &gd)) return false;
+	const KernelShape ks = mixconv_lookup(true, false, P, dp);
+	if (!ks) return false;
+	const MixradShape geom = mixrad_geom(ks.variant);
+	if (!geom.ok) return false;
+	const int sp = geom.sp, lutn = geom.lutn, groups = geom.groups, gd = geom.groupsDense;
 	if (gd <= 0 || sp <= 0) return false; // (an instance without the stage form — the registry leaves its geometry at zero: DST-I of 1782 reals, 2 * 1783 complex points, divided by it)
 	const uint64_t budget = sw.mixradLdsBytes;
 	const bool twoSets = ops && mixrad_two_sets((uint32_t)M, A);
-	c.P = P; c.M = M; c.A = A; c.len = len;
+	c.variant = ks.variant; c.fpw = ks.perWg; c.threads = ks.threads;
+	for (int k = 0; k < 5; k++) c.rad[k] = ks.sched[k];
+	c.P = P; c.M = M; c.A = A; c.len = ks.len;
 	// layout of the convolution's thread groups (kernel_mixrad.h MixradGeom): the wave-aligned one runs its rounds without workgroup barriers (a round costs about 0.8
 	// of a dense one: 3144, 3130, 3611, 314 1.2-1.5x faster) but may have fewer groups than the dense FPW — a round more where the cofactor was matched to FPW
 	// (3232 = 32 * 101, 2032 = 16 * 127: 0.9x).  Cost of a row = rounds per tile / rows per tile, per layout with its own tile
@@ -406,43 +423,40 @@ static int finish_pass(const PassBuild& bIn, Arena& ar, PassPlan& pp) {
 	// strided-tile passes of power-of-two length run on the hand-specialised column kernel
 	if (b.allowFast && b.fastKernel == KERNEL_GENERIC && b.colIn && b.L >= 2 && b.L <= 1024 && (b.L & (b.L - 1)) == 0 && b.preOp == OP_NONE
 	    && b.midOp == OP_NONE && (b.postOp == OP_NONE || b.postOp == OP_TWIDDLE_4STEP) && !b.realIn && !b.realOut && !b.forceT) {
-		int variant, bits[4], tc, thr;
 		const uint64_t esz = b.dp ? 16 : 8;
 		const HostDim d0 = b.dims.empty() ? HostDim{1, 0, 0} : b.dims[0];
 		const uint64_t spanIn = (b.L * (uint64_t)std::llabs(b.inStrideJ) + 64 * (uint64_t)std::llabs(d0.inStride)) * esz;
 		const uint64_t spanOut = (b.L * (uint64_t)std::llabs(b.outStrideJ) + 64 * (uint64_t)std::llabs(d0.outStride)) * esz;
-		if (pow2_col_lookup(ilog2(b.L), b.dp, Switches::shape(b.sw.pow2ColShape, ilog2(b.L)), &variant, bits, &tc, &thr)) {
+		if (const KernelShape ks = pow2_col_lookup(ilog2(b.L), b.dp, Switches::shape(b.sw.pow2ColShape, ilog2(b.L)))) {
 			b.bigSpan = b.sw.forceBigSpan || !(spanIn < kSpanLimit && spanOut < kSpanLimit); // (then the kernel's 64-bit form: DESIGN 7, the z axis of 1024^3 on one GPU)
-			b.fastKernel = KERNEL_POW2_COL; b.fastVariant = variant; b.fastThreads = thr; b.forceT = (uint32_t)tc;
+			b.fastKernel = KERNEL_POW2_COL; b.fastVariant = ks.variant; b.fastThreads = ks.threads; b.forceT = (uint32_t)ks.perWg;
 			b.radices.clear();
-			for (int k = 0; k < 4; k++) if (bits[k]) b.radices.push_back(1u << bits[k]);
+			for (int k = 0; k < 4; k++) if (ks.sched[k]) b.radices.push_back(1u << ks.sched[k]);
 		}
 	}
 	// real transforms (fused pre/post map) and strided C2C of curated lengths: op-FFT family
 	const bool fusedBluestein = b.preOp == OP_BLUESTEIN_PRE && b.midOp == OP_BLUESTEIN_MID && b.postOp == OP_BLUESTEIN_POST && !b.colIn && b.auxOff2ForPre == (size_t)-1;
 	const bool padMask = b.padInN || b.padOutN; // (the interpreter, pow2_row / pow2_col, the fused Bluestein kernels (rdMask / wrMask, round 4) and the op-FFT kernels honour the masks: Io64 / Io32 / explicit)
 	if (fusedBluestein && b.allowOp && b.fastKernel == KERNEL_GENERIC && (b.L & (b.L - 1)) == 0 && !b.forceT && b.radices.empty()) { // power-of-two padded length: register-resident persistent kernel
-		int variant, bits[4], fpw, thr;
 		const HostDim d0 = b.dims.empty() ? HostDim{1, 0, 0} : b.dims[0];
 		const uint64_t span = (b.L + 64 * (uint64_t)std::max<int64_t>(std::llabs(d0.inStride), std::llabs(d0.outStride))) * (b.dp ? 16 : 8);
-		if (span < kSpanLimit && b.opN * 2 <= b.L && pow2_blue_lookup(ilog2(b.L), b.dp, Switches::shape(b.sw.pow2BlueShape, ilog2(b.L)), &variant, bits, &fpw, &thr)) {
-			b.fastKernel = KERNEL_POW2_BLUE; b.fastVariant = variant; b.fastThreads = thr; b.forceT = (uint32_t)fpw;
+		if (span < kSpanLimit && b.opN * 2 <= b.L) if (const KernelShape ks = pow2_blue_lookup(ilog2(b.L), b.dp, Switches::shape(b.sw.pow2BlueShape, ilog2(b.L)))) {
+			b.fastKernel = KERNEL_POW2_BLUE; b.fastVariant = ks.variant; b.fastThreads = ks.threads; b.forceT = (uint32_t)ks.perWg;
 			b.radices.clear();
-			for (int k = 0; k < 4; k++) if (bits[k]) b.radices.push_back(1u << bits[k]);
+			for (int k = 0; k < 4; k++) if (ks.sched[k]) b.radices.push_back(1u << ks.sched[k]);
 		}
 	}
 	// ... and its column form for strided axes (tiles of neighbouring columns, one pass)
 	const bool fusedBluesteinCol = b.preOp == OP_BLUESTEIN_PRE && b.midOp == OP_BLUESTEIN_MID && b.postOp == OP_BLUESTEIN_POST && b.colIn && b.colOut && b.auxOff2ForPre == (size_t)-1;
 	if (fusedBluesteinCol && b.allowOp && b.fastKernel == KERNEL_GENERIC && (b.L & (b.L - 1)) == 0 && !b.forceT && b.radices.empty()) {
-		int variant, bits[4], tc, thr;
 		const uint64_t esz = b.dp ? 16 : 8;
 		const HostDim d0 = b.dims.empty() ? HostDim{1, 0, 0} : b.dims[0];
 		const uint64_t spanIn = (b.L * (uint64_t)std::llabs(b.inStrideJ) + 64 * (uint64_t)std::llabs(d0.inStride)) * esz;
 		const uint64_t spanOut = (b.L * (uint64_t)std::llabs(b.outStrideJ) + 64 * (uint64_t)std::llabs(d0.outStride)) * esz;
-		if (spanIn < kSpanLimit && spanOut < kSpanLimit && b.opN * 2 <= b.L && pow2_col_blue_lookup(ilog2(b.L), b.dp, 5, &variant, bits, &tc, &thr)) {
-			b.fastKernel = KERNEL_POW2_COL_BLUE; b.fastVariant = variant; b.fastThreads = thr; b.forceT = (uint32_t)tc;
+		if (spanIn < kSpanLimit && spanOut < kSpanLimit && b.opN * 2 <= b.L) if (const KernelShape ks = pow2_col_blue_lookup(ilog2(b.L), b.dp, 5)) {
+			b.fastKernel = KERNEL_POW2_COL_BLUE; b.fastVariant = ks.variant; b.fastThreads = ks.threads; b.forceT = (uint32_t)ks.perWg;
 			b.radices.clear();
-			for (int k = 0; k < 4; k++) if (bits[k]) b.radices.push_back(1u << bits[k]);
+			for (int k = 0; k < 4; k++) if (ks.sched[k]) b.radices.push_back(1u << ks.sched[k]);
 		}
 	}
 	// (column tile in, per-column contiguous run out = the first Four-Step pass: the transposed-store variant)
@@ -458,16 +472,15 @@ static int finish_pass(const PassBuild& bIn, Arena& ar, PassPlan& pp) {
 		// measured (tools/tune_mixed_ops.py, profiles/r03_short_real_rows_fused_maps_vs_instance_between_maps.jsonl): complex lengths 8 and 16 (R2C / DCT of 16 and
 		// 32 reals) run 1.1-5x faster between the maps; from 20 on the fused-map kernels win (only the powers of two were measured: the others keep their fused-map kernel)
 		const uint64_t lim = b.sw.mixedOpsMax;
-		int v, r5[5], f, t;
 		// (round 4: the other lengths of that range too — their fused-map instances are one thread per row, radix-10 / 14 / 15 butterflies fed by loads a row pitch
 		// apart per lane: DCT-IV of 20 and 30 reals ran at 0.19 / 0.14x the reference, DCT-II of 28 at 0.22x, profiles/r04_dct4_rows_5_400_*)
 		const bool rowOp = !b.colIn && !b.colOut && !padMask && b.inStrideJ == 1 && b.outStrideJ == 1 && (b.preOp != OP_NONE || b.postOp != OP_NONE);
-		preferMixedOps = lim && b.L >= 8 && b.L <= lim && rowOp && mixed_row_lookup(b.L, b.dp, &v, r5, &f, &t);
+		preferMixedOps = lim && b.L >= 8 && b.L <= lim && rowOp && mixed_row_lookup(b.L, b.dp);
 		// two real rows per transform exist only between the generic maps (PassParams::pairRows): VKFFT_MI355X_PAIR_PREFER=1 sends the pairable families there
 		// even where a fused-map instance exists (measurement switch)
 		const int pairPrefer = b.sw.pairPrefer;
 		const bool r2cFam = b.preOp == OP_R2C_FULL || b.preOp == OP_C2R_FULL || b.postOp == OP_R2C_FULL || b.postOp == OP_C2R_FULL;
-		if (!preferMixedOps && (pairPrefer == 1 || (pairPrefer == 2 && !r2cFam)) && rowOp && pairable_family(b.preOp, b.postOp, b.L, b.opN) && mixed_row_lookup(b.L, b.dp, &v, r5, &f, &t)) preferMixedOps = true;
+		if (!preferMixedOps && (pairPrefer == 1 || (pairPrefer == 2 && !r2cFam)) && rowOp && pairable_family(b.preOp, b.postOp, b.L, b.opN) && mixed_row_lookup(b.L, b.dp)) preferMixedOps = true;
 	}
 	if (b.allowOp && opMaskOK && !preferMixedOps && b.fastKernel == KERNEL_GENERIC && !b.forceT && b.midOp == OP_NONE && (b.colIn == b.colOut || transOut) && b.radices.empty()
 	    && !(b.preOp == OP_NONE && b.postOp == OP_NONE && !b.colIn)) {
@@ -476,10 +489,9 @@ static int finish_pass(const PassBuild& bIn, Arena& ar, PassPlan& pp) {
 		const uint64_t maxPos = std::max<uint64_t>(std::max<uint64_t>(b.L, b.inLen), std::max<uint64_t>(b.outLen, b.opN)) * 2 + 4;
 		const uint64_t spanIn = (maxPos * (uint64_t)std::llabs(b.inStrideJ) + 64 * (uint64_t)std::llabs(d0.inStride)) * ib;
 		const uint64_t spanOut = (maxPos * (uint64_t)std::llabs(b.outStrideJ) + 64 * (uint64_t)std::llabs(d0.outStride)) * ob;
-		int variant, rad5[5], fpw, thr;
-		if (spanIn < kSpanLimit && spanOut < kSpanLimit && opfft_lookup(b.L, b.dp, b.colIn, transOut, b.preOp, b.postOp, &variant, rad5, &fpw, &thr)) {
-			b.fastKernel = KERNEL_OPFFT; b.fastVariant = variant; b.fastThreads = thr; b.forceT = (uint32_t)fpw;
-			for (int k = 0; k < 5; k++) if (rad5[k] > 1) b.radices.push_back((uint32_t)rad5[k]);
+		if (spanIn < kSpanLimit && spanOut < kSpanLimit) if (const KernelShape ks = opfft_lookup(b.L, b.dp, b.colIn, transOut, b.preOp, b.postOp)) {
+			b.fastKernel = KERNEL_OPFFT; b.fastVariant = ks.variant; b.fastThreads = ks.threads; b.forceT = (uint32_t)ks.perWg;
+			for (int k = 0; k < 5; k++) if (ks.sched[k] > 1) b.radices.push_back((uint32_t)ks.sched[k]);
 		}
 	}
 	// real transforms on unit-stride rows whose complex length has a mixed-radix instance but no fused-map kernel above: the ahead-of-time transform
@@ -491,19 +503,18 @@ static int finish_pass(const PassBuild& bIn, Arena& ar, PassPlan& pp) {
 		if (b.allowOp && b.fastKernel == KERNEL_GENERIC && !b.forceT && b.midOp == OP_NONE && !b.colIn && !b.colOut && b.radices.empty() && !b.preNat && !b.postNat &&
 		    b.auxOff2ForPre == (size_t)-1 && (b.preOp != OP_NONE || b.postOp != OP_NONE) && realOp(b.preOp) && realOp(b.postOp) && b.inStrideJ == 1 && b.outStrideJ == 1 &&
 		    !b.sw.noMixedOps) {
-			int variant, rad5[5], fpw, thr;
-			uint64_t len = 0;
 			opsCplxLen = b.L;
 			// (the maps inside the stages address the rows of a tile — up to 2 * FPW <= 128 of them — with 32-bit byte offsets from the tile's base: a row pitch that
 			// takes the tile past 2 GiB leaves the pass to the interpreter, as on the complex paths)
 			const HostDim d0o = b.dims.empty() ? HostDim{1, 0, 0} : b.dims[0];
 			const bool spanOK = (2 * b.L + 128 * (uint64_t)std::max<int64_t>(std::llabs(d0o.inStride), std::llabs(d0o.outStride))) * (b.dp ? 16 : 8) < kSpanLimit;
+			KernelShape ks;
 			if (!spanOK) { /* interpreter */ }
-			else if (mixed_row_lookup(b.L, b.dp, &variant, rad5, &fpw, &thr)) {
-				const int fo = mixed_row_ops_fpw(variant); // (the form between the maps may take fewer rows per workgroup: kernel_mixed.h mixed_ops_fpw)
-				if (fo > 0 && fo != fpw) { thr = thr / fpw * fo; fpw = fo; }
-				b.fastKernel = KERNEL_MIXED_ROW; b.fastVariant = variant; b.fastThreads = thr; b.forceT = (uint32_t)fpw;
-				for (int k = 0; k < 5; k++) if (rad5[k] > 1) b.radices.push_back((uint32_t)rad5[k]);
+			else if ((ks = mixed_row_lookup(b.L, b.dp))) {
+				const int fo = mixed_row_ops_fpw(ks.variant); // (the form between the maps may take fewer rows per workgroup: kernel_mixed.h mixed_ops_fpw)
+				if (fo > 0 && fo != ks.perWg) { ks.threads = ks.threads / ks.perWg * fo; ks.perWg = fo; }
+				b.fastKernel = KERNEL_MIXED_ROW; b.fastVariant = ks.variant; b.fastThreads = ks.threads; b.forceT = (uint32_t)ks.perWg;
+				for (int k = 0; k < 5; k++) if (ks.sched[k] > 1) b.radices.push_back((uint32_t)ks.sched[k]);
 			} else if (!padMask && tm_family(b.preOp, b.postOp, b.L, b.opN) != TM_NONE && !b.sw.noTmaps && [&]() {
 				// the complex length is M * P with a Rader prime and a served cofactor: mixrad_kernel between the table-driven maps (kernel_mixrad.h, kernel_tmaps.h)
 				MixradChoice mr;
@@ -522,7 +533,7 @@ static int finish_pass(const PassBuild& bIn, Arena& ar, PassPlan& pp) {
 				for (int k = 0; k < 5; k++) if (mr.rad[k] > 1) b.radices.push_back((uint32_t)mr.rad[k]);
 				return true;
 			}()) {
-			} else if (b.L >= 37 && is_prime_u(b.L) && mixconv_lookup(true, false, b.L, b.dp, &variant, &len, rad5, &fpw, &thr)) {
+			} else if (b.L >= 37 && is_prime_u(b.L) && (ks = mixconv_lookup(true, false, b.L, b.dp))) {
 				// the complex length is a Rader prime: mixconv_kernel OPS = 1 (transform length P - 1; kernel spectrum through aux3)
 				const uint64_t P = b.L;
 				if (!b.inLen) b.inLen = (uint32_t)P;
@@ -531,9 +542,9 @@ static int finish_pass(const PassBuild& bIn, Arena& ar, PassPlan& pp) {
 				size_t bhatOff;
 				make_mixconv_rader_tables(P, b.dp, ar, mixconvTabOff, bhatOff);
 				b.auxOff2ForPre = bhatOff;
-				b.L = len;
-				b.fastKernel = KERNEL_MIXCONV; b.fastVariant = variant; b.fastThreads = thr; b.forceT = (uint32_t)fpw;
-				for (int k = 0; k < 5; k++) if (rad5[k] > 1) b.radices.push_back((uint32_t)rad5[k]);
+				b.L = ks.len;
+				b.fastKernel = KERNEL_MIXCONV; b.fastVariant = ks.variant; b.fastThreads = ks.threads; b.forceT = (uint32_t)ks.perWg;
+				for (int k = 0; k < 5; k++) if (ks.sched[k] > 1) b.radices.push_back((uint32_t)ks.sched[k]);
 			}
 		}
 	}
@@ -800,10 +811,8 @@ static bool is_supported_len(uint64_t L, uint32_t directMax) {
 // a factor length the hand-specialised column kernels serve in all three Four-Step roles (first pass with transposed store,
 // middle pass with twiddle, last pass)
 static bool fast_col_len(uint64_t L, bool dp) {
-	int v, r5[5], bits[4], f, t;
-	if ((L & (L - 1)) == 0 && L >= 16 && L <= 1024) return pow2_col_lookup(ilog2(L), dp, 0, &v, bits, &f, &t); // (whether the length is served: every shape index finds one)
-	return opfft_lookup(L, dp, true, true, OP_NONE, OP_TWIDDLE_4STEP, &v, r5, &f, &t) && opfft_lookup(L, dp, true, false, OP_NONE, OP_TWIDDLE_4STEP, &v, r5, &f, &t)
-	       && opfft_lookup(L, dp, true, false, OP_NONE, OP_NONE, &v, r5, &f, &t);
+	if ((L & (L - 1)) == 0 && L >= 16 && L <= 1024) return (bool)pow2_col_lookup(ilog2(L), dp, 0); // (whether the length is served: every shape index finds one)
+	return opfft_lookup(L, dp, true, true, OP_NONE, OP_TWIDDLE_4STEP) && opfft_lookup(L, dp, true, false, OP_NONE, OP_TWIDDLE_4STEP) && opfft_lookup(L, dp, true, false, OP_NONE, OP_NONE);
 }
 
 static bool choose_split(uint64_t N, bool dp, uint64_t maxLds, uint32_t directMax, bool fast, std::vector<uint64_t>& out) {
@@ -1061,8 +1070,8 @@ static bool emit_fused(const TransformDesc& d, const AxisJob& j, Arena& ar, Dire
 	if (!d.sw.fused || d.disableFastKernels || (j.N & (j.N - 1)) != 0 || j.inStrideJ != 1 || j.outStrideJ != 1) return false;
 	const bool dp = j.dp;
 	const uint64_t es = dp ? 16 : 8;
-	int variant, la, lb, bitsA[4], bitsB[4], tca, tcb, thr, wgPerCu;
-	if (!pow2_fused_lookup(ilog2(j.N), dp, d.sw.fusedMode, Switches::shape(d.sw.pow2FusedShape, ilog2(j.N)), &variant, &la, &lb, bitsA, bitsB, &tca, &tcb, &thr, &wgPerCu)) return false;
+	const FusedShape v = pow2_fused_lookup(ilog2(j.N), dp, d.sw.fusedMode, Switches::shape(d.sw.pow2FusedShape, ilog2(j.N)));
+	if (!v) return false;
 	// one batch progression
 	uint64_t batch = 1; int64_t inS = (int64_t)j.N, outS = (int64_t)j.N; bool first = true;
 	for (const HostDim& o : j.others) {
@@ -1071,8 +1080,8 @@ static bool emit_fused(const TransformDesc& d, const AxisJob& j, Arena& ar, Dire
 		else { if (o.inStride != inS * (int64_t)batch || o.outStride != outS * (int64_t)batch) return false; batch *= o.count; }
 	}
 	if (inS < (int64_t)j.N || outS < (int64_t)j.N || batch >= (1ull << 31)) return false;
-	const uint64_t n0 = 1ull << la, n1 = 1ull << lb;
-	const uint64_t tileBytes = n0 * (uint64_t)tca * es, fftBytes = j.N * es;
+	const uint64_t n0 = 1ull << v.n0, n1 = 1ull << v.n1;
+	const uint64_t tileBytes = n0 * (uint64_t)v.tca * es, fftBytes = j.N * es;
 	const uint32_t logTiles = ilog2(fftBytes / tileBytes);
 	// chunk: about a MiB of transforms, dealt round-robin to Q queues (one per XCD when there are enough chunks).  Tickets of a queue
 	// are handed out in order, so at any moment its Wq workgroups hold a window of about Wq consecutive tickets.  A wait is avoided
@@ -1089,11 +1098,11 @@ static bool emit_fused(const TransformDesc& d, const AxisJob& j, Arena& ar, Dire
 	// (2^22 fp32: a transform is 32 MiB, the budget decides between lag 3 / ring 6 and lag 4 / ring 8 — measured 2.73 against 3.04 TB/s with the tiles of two
 	// halves, profiles/r05_fused_lag_ring_pairs.jsonl: with lag 3 a tile waits 5-10 k cycles per ticket for the previous tenant of its ring slot)
 	const uint64_t ringBudget = fftBytes >= (32ull << 20) ? (256ull << 20) : (224ull << 20);
-	const uint64_t wgs = 256ull * (uint64_t)(d.sw.fusedWgPerCu ? d.sw.fusedWgPerCu : wgPerCu);
+	const uint64_t wgs = 256ull * (uint64_t)(d.sw.fusedWgPerCu ? d.sw.fusedWgPerCu : v.wgPerCu);
 	// measured (tools/tune_fused.py): completions are published up to a ticket late and the ticket rate rises with the speed of the
 	// kernel, so the window is taken generously: 3 windows where two or more workgroups share a CU, 2 with one workgroup per CU
 	// (round 4, pipelined form of 2^19 / 2^20: one workgroup per CU, but the A tile of the NEXT ticket is requested early: 3 windows measured +2.7 % over 2)
-	uint64_t marginPct = d.sw.fusedMarginPct ? d.sw.fusedMarginPct : ((wgPerCu >= 2 || (!dp && j.N <= (1ull << 20))) ? 300 : 200);
+	uint64_t marginPct = d.sw.fusedMarginPct ? d.sw.fusedMarginPct : ((v.wgPerCu >= 2 || (!dp && j.N <= (1ull << 20))) ? 300 : 200);
 	uint64_t Q = 1, X = 1, D = 1, NS = 1, Cq = C;
 	auto shape = [&](uint64_t q, uint64_t pct) {
 		Q = q; Cq = (C + Q - 1) / Q;
@@ -1119,11 +1128,11 @@ static bool emit_fused(const TransformDesc& d, const AxisJob& j, Arena& ar, Dire
 	PassPlan pp;
 	memset(&pp.prm, 0, sizeof(pp.prm));
 	pp.prm.L = (uint32_t)std::min<uint64_t>(j.N, 0xffffffffu);
-	pp.kernel = KERNEL_POW2_FUSED; pp.variant = variant; pp.threads = (uint32_t)thr; pp.dp = dp;
+	pp.kernel = KERNEL_POW2_FUSED; pp.variant = v.variant; pp.threads = (uint32_t)v.thr; pp.dp = dp;
 	pp.inRole = j.inRole; pp.outRole = j.outRole; pp.inElemBytes = pp.outElemBytes = (int)es;
 	pp.label = "4step-fused";
-	pp.lutOff = build_pow2_stage_lut(ar, bitsA, dp);
-	pp.fusedLutBOff = build_pow2_stage_lut(ar, bitsB, dp);
+	pp.lutOff = build_pow2_stage_lut(ar, v.radA, dp);
+	pp.fusedLutBOff = build_pow2_stage_lut(ar, v.radB, dp);
 	{ // two-level Four-Step table w_N^e = lo[e & mask] * hi[e >> bits]  (vkFFT_4step.h:31 computes the same factor per element)
 		const uint32_t lo = (ceil_log2(j.N) + 1) / 2;
 		const uint64_t nlo = 1ull << lo, nhi = (j.N + nlo - 1) / nlo;
@@ -1175,8 +1184,7 @@ static size_t build_mix_stage_lut(Arena& ar, const int rad[5], bool dp) {
 
 // Fused Four-Step of a NON-power-of-two two-factor length (kernel_mix_fused.h): the same launch shape as emit_fused (chunks, queues, lag, ring), tiles of either
 // phase that need not divide their factor.  One launch of `batch` transforms of M = n0 * n1 points, inS / outS elements apart on either side.
-struct MixFusedShape { int variant, n0, n1, radA[5], radB[5], tca, tcb, thr, wgPerCu; };
-static bool build_mix_fused_pass(const TransformDesc& d, bool dp, uint64_t M, const MixFusedShape& v, uint64_t batch, int64_t inS, int64_t outS, bool inverse, double scale,
+static bool build_mix_fused_pass(const TransformDesc& d, bool dp, uint64_t M, const FusedShape& v, uint64_t batch, int64_t inS, int64_t outS, bool inverse, double scale,
                                  Arena& ar, PassPlan& pp, uint64_t& scratch) {
 	const uint64_t es = dp ? 16 : 8;
 	const uint64_t n0 = (uint64_t)v.n0, n1 = (uint64_t)v.n1;
@@ -1252,8 +1260,8 @@ static bool one_batch_progression(const AxisJob& j, uint64_t& batch, int64_t& in
 static bool emit_mix_fused(const TransformDesc& d, const AxisJob& j, Arena& ar, DirectionPlan& out, std::vector<PassPlan>& passes) {
 	if (!d.sw.fused || d.disableFastKernels || (j.N & (j.N - 1)) == 0 || j.inStrideJ != 1 || j.outStrideJ != 1) return false;
 	if (d.sw.mixFused == 0) return false;
-	MixFusedShape v;
-	if (!mix_fused_lookup(j.N, j.dp, d.sw.mixFusedShape, &v.variant, &v.n0, &v.n1, v.radA, v.radB, &v.tca, &v.tcb, &v.thr, &v.wgPerCu)) return false;
+	const FusedShape v = mix_fused_lookup(j.N, j.dp, d.sw.mixFusedShape);
+	if (!v) return false;
 	uint64_t batch; int64_t inS, outS;
 	if (!one_batch_progression(j, batch, inS, outS)) return false;
 	PassPlan pp; uint64_t scratch = 0;
@@ -1281,8 +1289,8 @@ static bool emit_mix_fused_blue(const TransformDesc& d, const AxisJob& j, Arena&
 	// and the instances with the hooks sit at the 128-register cap.  Off unless asked for; what would win is ONE launch with both intermediates in the ring.
 	if (d.sw.mixFusedBlue == 0) return false;
 	const uint64_t N = j.N;
-	MixFusedShape v;
-	if (!mix_fused_lookup((2 * N - 1) | kMixFusedBlueQuery, false, 0, &v.variant, &v.n0, &v.n1, v.radA, v.radB, &v.tca, &v.tcb, &v.thr, &v.wgPerCu)) return false;
+	const FusedShape v = mix_fused_lookup((2 * N - 1) | kMixFusedBlueQuery, false, 0);
+	if (!v) return false;
 	const uint64_t M = (uint64_t)v.n0 * (uint64_t)v.n1;
 	uint64_t batch; int64_t inS, outS;
 	if (!one_batch_progression(j, batch, inS, outS)) return false;
@@ -1428,30 +1436,21 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 	// 1.1-1.3 TB/s, the fused chirp-z kernel at 1.5-2 TB/s)
 	uint64_t fusedM = 0;
 	bool smoothNoInstance = false;
-	if (unit && !d.disableFastKernels && smooth13(j.N) && (j.N & (j.N - 1)) != 0 && j.N > 1024 && j.N <= 4096) {
-		int v, r5[5], f, t;
-		smoothNoInstance = !mixed_row_lookup(j.N, dp, &v, r5, &f, &t);
-	}
+	if (unit && !d.disableFastKernels && smooth13(j.N) && (j.N & (j.N - 1)) != 0 && j.N > 1024 && j.N <= 4096) smoothNoInstance = !mixed_row_lookup(j.N, dp);
 	// lengths with a direct prime butterfly (17 .. 31: tools/gen_mixed_table.py DIRECT_PRIMES) among their radices stay on the radix kernels where an
 	// instance exists (rows: every such length up to 4096; strided axes: the pure primes)
 	bool nativeInstance = false;
-	if (!d.disableFastKernels && !smooth13(j.N) && j.N <= 4096) {
-		int v, r5[5], f, t;
-		nativeInstance = unit ? mixed_row_lookup(j.N, dp, &v, r5, &f, &t) : opfft_lookup(j.N, dp, true, false, OP_NONE, OP_NONE, &v, r5, &f, &t);
-	}
+	if (!d.disableFastKernels && !smooth13(j.N) && j.N <= 4096) nativeInstance = (bool)(unit ? mixed_row_lookup(j.N, dp) : opfft_lookup(j.N, dp, true, false, OP_NONE, OP_NONE));
 	if (unit && !nativeInstance && !d.disableFastKernels && !d.forceBluesteinSize && !d.fixMaxRadixBluestein && (!smooth13(j.N) || smoothNoInstance)) {
-		const uint64_t rowPitch = j.others.empty() ? j.N : (uint64_t)std::max<int64_t>(std::llabs(j.others[0].inStride), std::llabs(j.others[0].outStride));
-		uint64_t Mp = 64; while (Mp < 2 * j.N - 1) Mp *= 2; // measured: the power-of-two padded length wins even at 1.6x the {1,3,5}*2^k one
-		int v, bits[4], fpw, thr;
-		if ((rowPitch * 64 + j.N) * (dp ? 16 : 8) < kSpanLimit && pow2_blue_lookup(ilog2(Mp), dp, Switches::shape(d.sw.pow2BlueShape, ilog2(Mp)), &v, bits, &fpw, &thr)) fusedM = Mp;
+		const uint64_t Mp = blue_pow2_len(j.N, 64); // measured: the power-of-two padded length wins even at 1.6x the {1,3,5}*2^k one
+		if (tile64_in_span(row_pitch(j.others, j.N), j.N, dp ? 16 : 8) && pow2_blue_lookup(ilog2(Mp), dp, Switches::shape(d.sw.pow2BlueShape, ilog2(Mp)))) fusedM = Mp;
 	}
 	if (!unit && !nativeInstance && !d.disableFastKernels && !d.forceBluesteinSize && !d.fixMaxRadixBluestein && !smooth13(j.N) && !j.others.empty()
 	    && j.others[0].inStride == 1 && j.others[0].outStride == 1) {
 		// strided axes of non-smooth length (prime x prime planes): the one-pass column Bluestein kernel on the power-of-two padded length beats
 		// the interpreter's Rader / Bluestein stages by 3-6x (measured on the reference's sample-7 systems)
-		uint64_t Mp = 64; while (Mp < 2 * j.N - 1) Mp *= 2;
-		int v, bits[4], tc, thr;
-		if (pow2_col_blue_lookup(ilog2(Mp), dp, 5, &v, bits, &tc, &thr)) fusedM = Mp;
+		const uint64_t Mp = blue_pow2_len(j.N, 64);
+		if (pow2_col_blue_lookup(ilog2(Mp), dp, 5)) fusedM = Mp;
 	}
 	// ... or the one-kernel cyclic convolution on a smooth transform length (kernel_mixconv.h), unit-stride rows and tiles of neighbouring columns of a
 	// strided axis: Rader for a prime with 13-smooth p-1 (p-1 points, no padding), Bluestein on the smallest ladder length >= 2N-1.  Against the
@@ -1461,12 +1460,11 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 	// stage of the row (kernel_mixrad.h; the reference's Rader stage inside its radix kernels, vkFFT_Scheduler.h:1733-1873).  VKFFT_MI355X_MIXRAD=0: off
 	if (unit && !padded && !nativeInstance && !d.disableFastKernels && !d.forceBluesteinSize && !d.fixMaxRadixBluestein && !smooth13(j.N)) {
 		MixradChoice mr;
-		const uint64_t rowPitch = j.others.empty() ? j.N : (uint64_t)std::max<int64_t>(std::llabs(j.others[0].inStride), std::llabs(j.others[0].outStride));
 		// taken where it is faster than the fused Bluestein kernel on the next power of two M2 >= 2N - 1 (every served length forced either way on the device).  A point of
 		// the row costs c points of the padded power-of-two transform; Bluestein's 8192-point rows leave one workgroup per CU: 1.5 per point
-		uint64_t M2 = 64; while (M2 < 2 * j.N - 1) M2 *= 2;
+		const uint64_t M2 = blue_pow2_len(j.N, 64);
 		const bool radForced = d.sw.mixrad == 2; // (tests: always)
-		bool radTake = mixrad_choose(d.sw, j.N, dp, false, mr) && (rowPitch * 64 + j.N) * (dp ? 16 : 8) < kSpanLimit;
+		bool radTake = mixrad_choose(d.sw, j.N, dp, false, mr) && tile64_in_span(row_pitch(j.others, j.N), j.N, dp ? 16 : 8);
 		if (radTake) {
 			const double c = d.sw.mixradCost != d.sw.mixradCost ? mr.cost : d.sw.mixradCost; // (unset: the model)
 			radTake = radForced || c * (double)j.N < (double)M2 * (M2 >= 8192 ? 1.5 : 1.0);
@@ -1491,7 +1489,7 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 			return 0;
 		}
 	}
-	struct { bool use = false, rader = false, col = false; int variant = -1; uint64_t len = 0; int rad[5] = {1, 1, 1, 1, 1}; int fpw = 0, thr = 0; } mc;
+	struct { bool use = false, rader = false, col = false; KernelShape ks; } mc;
 	const bool colTile = !unit && !j.others.empty() && j.others[0].inStride == 1 && j.others[0].outStride == 1;
 	if ((unit || colTile) && !nativeInstance && !d.disableFastKernels && !d.forceBluesteinSize && !d.fixMaxRadixBluestein && (!smooth13(j.N) || (unit && smoothNoInstance))) {
 		const int mode = d.sw.mixconv;
@@ -1500,29 +1498,27 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 		const double kPow2Big = 1.9; // the power-of-two kernel at its longest padded length (128 KiB per row, one workgroup per CU) costs that much more per point
 		const uint64_t esz = dp ? 16 : 8;
 		bool spanOK;
-		if (unit) {
-			const uint64_t rowPitch = j.others.empty() ? j.N : (uint64_t)std::max<int64_t>(std::llabs(j.others[0].inStride), std::llabs(j.others[0].outStride));
-			spanOK = (rowPitch * 64 + j.N) * esz < kSpanLimit;
-		} else spanOK = (2 * j.N * (uint64_t)std::max<int64_t>(std::llabs(j.inStrideJ), std::llabs(j.outStrideJ)) + 64) * esz < kSpanLimit;
+		if (unit) spanOK = tile64_in_span(row_pitch(j.others, j.N), j.N, esz);
+		else spanOK = (2 * j.N * (uint64_t)std::max<int64_t>(std::llabs(j.inStrideJ), std::llabs(j.outStrideJ)) + 64) * esz < kSpanLimit;
 		if (mode && spanOK) {
 			double best = fusedM && mode < 2 ? (double)fusedM * (fusedM * esz >= (128ull << 10) ? kPow2Big : 1.0) : 1e300;
-			int v, r5[5], f, t; uint64_t len;
-			if (is_prime_u(j.N) && mixconv_lookup(true, !unit, j.N, dp, &v, &len, r5, &f, &t) && kCostRader * (double)len < best) {
-				best = kCostRader * (double)len;
-				mc.use = true; mc.rader = true; mc.variant = v; mc.len = len; mc.fpw = f; mc.thr = t; for (int k = 0; k < 5; k++) mc.rad[k] = r5[k];
+			KernelShape ks;
+			if (is_prime_u(j.N) && (ks = mixconv_lookup(true, !unit, j.N, dp)) && kCostRader * (double)ks.len < best) {
+				best = kCostRader * (double)ks.len;
+				mc.use = true; mc.rader = true; mc.ks = ks;
 			}
-			if (mixconv_lookup(false, !unit, 2 * j.N - 1, dp, &v, &len, r5, &f, &t) && kCostBlue * (double)len < best) {
-				best = kCostBlue * (double)len;
-				mc.use = true; mc.rader = false; mc.variant = v; mc.len = len; mc.fpw = f; mc.thr = t; for (int k = 0; k < 5; k++) mc.rad[k] = r5[k];
+			if ((ks = mixconv_lookup(false, !unit, 2 * j.N - 1, dp)) && kCostBlue * (double)ks.len < best) {
+				best = kCostBlue * (double)ks.len;
+				mc.use = true; mc.rader = false; mc.ks = ks;
 			}
 			mc.col = !unit;
 		}
 	}
 	if (mc.use) {
 		const uint64_t N = j.N;
-		b.L = mc.len; b.inLen = b.outLen = (uint32_t)N; b.opN = (uint32_t)N;
-		for (int k = 0; k < 5; k++) if (mc.rad[k] > 1) b.radices.push_back((uint32_t)mc.rad[k]);
-		b.fastKernel = KERNEL_MIXCONV; b.fastVariant = mc.variant; b.fastThreads = mc.thr; b.forceT = (uint32_t)mc.fpw;
+		b.L = mc.ks.len; b.inLen = b.outLen = (uint32_t)N; b.opN = (uint32_t)N;
+		for (int k = 0; k < 5; k++) if (mc.ks.sched[k] > 1) b.radices.push_back((uint32_t)mc.ks.sched[k]);
+		b.fastKernel = KERNEL_MIXCONV; b.fastVariant = mc.ks.variant; b.fastThreads = mc.ks.threads; b.forceT = (uint32_t)mc.ks.perWg;
 		b.bsSwapIn = b.bsSwapOut = j.inverse; b.scale = j.scale;
 		b.inStrideJ = j.inStrideJ; b.outStrideJ = j.outStrideJ; b.dims = j.others;
 		b.colIn = b.colOut = mc.col;
@@ -1534,7 +1530,7 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 			b.label = "rader";
 		} else {
 			size_t chirpOff, bhatOff;
-			make_bluestein_tables(N, mc.len, dp, ar, chirpOff, bhatOff);
+			make_bluestein_tables(N, mc.ks.len, dp, ar, chirpOff, bhatOff);
 			b.preOp = OP_BLUESTEIN_PRE; b.midOp = OP_BLUESTEIN_MID; b.postOp = OP_BLUESTEIN_POST;
 			b.auxOff = chirpOff; b.aux2Off = bhatOff;
 			b.label = "bluestein";
@@ -1550,11 +1546,10 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 		// a strided axis of non-smooth length beyond the reach of the column Bluestein kernel (padded length above 2048): transpose it against its
 		// unit-stride companion into a dense scratch copy, run it there as unit-stride rows (the fused Bluestein row kernel) and transpose back.
 		// Two extra passes at copy speed instead of an interpreter pass with two columns per workgroup (1087 x 1087: 0.23 -> 0.9 TB/s).
-		uint64_t Mp = 64; while (Mp < 2 * j.N - 1) Mp *= 2;
-		int v, bits[4], fpw, thr;
+		const uint64_t Mp = blue_pow2_len(j.N, 64);
 		const uint64_t C = j.others[0].count;
 		uint64_t outer = 1; for (size_t i = 1; i < j.others.size(); i++) outer *= j.others[i].count;
-		if (pow2_blue_lookup(ilog2(Mp), dp, Switches::shape(d.sw.pow2BlueShape, ilog2(Mp)), &v, bits, &fpw, &thr) && C * j.N * outer < (1ull << 40)) {
+		if (pow2_blue_lookup(ilog2(Mp), dp, Switches::shape(d.sw.pow2BlueShape, ilog2(Mp))) && C * j.N * outer < (1ull << 40)) {
 			const size_t mark = passes.size();
 			auto transpose = [&](bool back) {
 				PassPlan t; memset(&t.prm, 0, sizeof(t.prm));
@@ -1607,7 +1602,7 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 		if (unit && !fusedM && !padded && 2 * N - 1 > cap && emit_mix_fused_blue(d, j, ar, out, passes)) return 0; // longer than one pass holds: two fused launches
 		if (unit && !fusedM && !d.disableFastKernels && !d.forceBluesteinSize && !d.fixMaxRadixBluestein) {
 			// multi-pass rows: a power-of-two padded length runs as three passes on the column kernels (below)
-			uint64_t Mp = 1; while (Mp < 2 * N - 1) Mp *= 2;
+			const uint64_t Mp = blue_pow2_len(N, 1);
 			if (Mp > cap && Mp * (dp ? 16 : 8) <= (1ull << 30)) M = Mp; // 32-bit byte offsets inside one padded row (buffer addressing)
 		}
 		std::vector<uint64_t> spM;
@@ -1616,7 +1611,7 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 			// M must split into column-kernel lengths; prefer a power of two when the smooth size does not split well
 			if (!choose_split(M, dp, d.maxLds, dmax, !d.disableFastKernels, spM)) {
 				if (d.forceBluesteinSize) return 3002;
-				M = 1; while (M < 2 * N - 1) M *= 2;
+				M = blue_pow2_len(N, 1);
 				if (!choose_split(M, dp, d.maxLds, dmax, !d.disableFastKernels, spM)) return 3002;
 			}
 		}
@@ -1627,9 +1622,8 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 			// power-of-two padded length whose two factors are column-kernel lengths: three passes (kernel_pow2.h,
 			// pow2_col_blue_kernel) — the middle one is FFT over m, * FFT(chirp), inverse FFT over m in registers
 			const uint64_t n0 = spM[0], n1 = M / n0;
-			int v1, v2, v3, bits1[4], bits2[4], bits3[4], tc1, tc2, tc3, th1, th2, th3;
-			if (pow2_col_blue_lookup(ilog2(n0), dp, 1, &v1, bits1, &tc1, &th1) && pow2_col_blue_lookup(ilog2(n1), dp, 2, &v2, bits2, &tc2, &th2)
-			    && pow2_col_blue_lookup(ilog2(n0), dp, 3, &v3, bits3, &tc3, &th3)) {
+			const KernelShape k1 = pow2_col_blue_lookup(ilog2(n0), dp, 1), k2 = pow2_col_blue_lookup(ilog2(n1), dp, 2), k3 = pow2_col_blue_lookup(ilog2(n0), dp, 3);
+			if (k1 && k2 && k3) {
 				uint64_t nsub = 1;
 				for (auto& o : j.others) nsub *= o.count;
 				std::vector<HostDim> dense = j.others;
@@ -1639,10 +1633,10 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 					for (size_t i = 0; i < j.others.size(); i++) r.push_back({j.others[i].count, inKind ? dense[i].inStride : j.others[i].inStride, outKind ? dense[i].outStride : j.others[i].outStride});
 					return r;
 				};
-				auto setFast = [&](PassBuild& q, int variant, const int bits[4], int tc, int thr) {
-					q.fastKernel = KERNEL_POW2_COL_BLUE; q.fastVariant = variant; q.fastThreads = thr; q.forceT = (uint32_t)tc;
+				auto setFast = [&](PassBuild& q, const KernelShape& ks) {
+					q.fastKernel = KERNEL_POW2_COL_BLUE; q.fastVariant = ks.variant; q.fastThreads = ks.threads; q.forceT = (uint32_t)ks.perWg;
 					q.radices.clear();
-					for (int k = 0; k < 4; k++) if (bits[k]) q.radices.push_back(1u << bits[k]);
+					for (int k = 0; k < 4; k++) if (ks.sched[k]) q.radices.push_back(1u << ks.sched[k]);
 					q.noCollapse = true;
 				};
 				PassBuild a = b;
@@ -1651,13 +1645,13 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 				a.preOp = OP_BLUESTEIN_PRE; a.auxOff2ForPre = chirpOff; a.bsSwapIn = j.inverse; a.opN = (uint32_t)N; a.opStrideJ = (uint32_t)n1; a.opStride0 = 1;
 				a.postOp = OP_TWIDDLE_4STEP; a.fsN = M; a.fsColDiv = 1;
 				a.inRole = j.inRole; a.outRole = ROLE_TEMP; a.label = "bluestein-1";
-				setFast(a, v1, bits1, tc1, th1);
+				setFast(a, k1);
 				PassBuild m2 = b;
 				m2.L = n1; m2.inStrideJ = m2.outStrideJ = (int64_t)n0; m2.colIn = m2.colOut = true;
 				m2.dims = withOthers({n0, 1, 1}, 1, 1);
 				m2.midOp = OP_BLUESTEIN_MID; m2.aux2Off = bhatOff; m2.opStrideJ = (uint32_t)n0; m2.opStride0 = 1; m2.opStride1 = 0;
 				m2.inRole = m2.outRole = ROLE_TEMP; m2.label = "bluestein-2";
-				setFast(m2, v2, bits2, tc2, th2);
+				setFast(m2, k2);
 				PassBuild c3 = b;
 				c3.L = n0; c3.inStrideJ = 1; c3.outStrideJ = (int64_t)n1; c3.colIn = c3.colOut = true;
 				c3.dims = withOthers({n1, (int64_t)n0, 1}, 1, 0);
@@ -1665,7 +1659,7 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 				c3.postOp = OP_BLUESTEIN_POST; c3.auxOff2ForPre = chirpOff; c3.bsSwapOut = j.inverse; c3.opN = (uint32_t)N; c3.opStrideJ = (uint32_t)n1; c3.opStride0 = 1;
 				c3.scale = j.scale;
 				c3.inRole = ROLE_TEMP; c3.outRole = j.outRole; c3.label = "bluestein-3";
-				setFast(c3, v3, bits3, tc3, th3);
+				setFast(c3, k3);
 				for (PassBuild* q : {&a, &m2, &c3}) { PassPlan pp; int r = finish_pass(*q, ar, pp); if (r) return r; passes.push_back(pp); }
 				out.uploadsPerAxis[j.axisIndex] = 3;
 				out.tempBytes = std::max<uint64_t>(out.tempBytes, nsub * M * es);
@@ -1675,10 +1669,9 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 		if (spM.size() == 3 && (M & (M - 1)) == 0 && !d.disableFastKernels) {
 			// three factors: five passes (see pow2_col_blue_kernel) instead of the seven of two Four-Step transforms + multiply
 			const uint64_t n0 = spM[0], n1 = spM[1], n2 = spM[2], M1 = n1 * n2;
-			int v1, v3, v4, v5, vb, bits1[4], bits3[4], bits4[4], bits5[4], bitsb[4], tc1, tc3, tc4, tc5, tcb, th1, th3, th4, th5, thb;
-			if (pow2_col_blue_lookup(ilog2(n0), dp, 1, &v1, bits1, &tc1, &th1) && pow2_col_lookup(ilog2(n1), dp, Switches::shape(d.sw.pow2ColShape, ilog2(n1)), &vb, bitsb, &tcb, &thb)
-			    && pow2_col_blue_lookup(ilog2(n2), dp, 2, &v3, bits3, &tc3, &th3) && pow2_col_blue_lookup(ilog2(n1), dp, 4, &v4, bits4, &tc4, &th4)
-			    && pow2_col_blue_lookup(ilog2(n0), dp, 3, &v5, bits5, &tc5, &th5)) {
+			const KernelShape k1 = pow2_col_blue_lookup(ilog2(n0), dp, 1), kb = pow2_col_lookup(ilog2(n1), dp, Switches::shape(d.sw.pow2ColShape, ilog2(n1)));
+			const KernelShape k3 = pow2_col_blue_lookup(ilog2(n2), dp, 2), k4 = pow2_col_blue_lookup(ilog2(n1), dp, 4), k5 = pow2_col_blue_lookup(ilog2(n0), dp, 3);
+			if (k1 && kb && k3 && k4 && k5) {
 				uint64_t nsub = 1;
 				for (auto& o : j.others) nsub *= o.count;
 				std::vector<HostDim> dense = j.others;
@@ -1687,10 +1680,10 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 					for (size_t i = 0; i < j.others.size(); i++) lead.push_back({j.others[i].count, inKind ? dense[i].inStride : j.others[i].inStride, outKind ? dense[i].outStride : j.others[i].outStride});
 					return lead;
 				};
-				auto setFast = [&](PassBuild& q, int kernel, int variant, const int bits[4], int tc, int thr) {
-					q.fastKernel = kernel; q.fastVariant = variant; q.fastThreads = thr; q.forceT = (uint32_t)tc;
+				auto setFast = [&](PassBuild& q, int kernel, const KernelShape& ks) {
+					q.fastKernel = kernel; q.fastVariant = ks.variant; q.fastThreads = ks.threads; q.forceT = (uint32_t)ks.perWg;
 					q.radices.clear();
-					for (int k = 0; k < 4; k++) if (bits[k]) q.radices.push_back(1u << bits[k]);
+					for (int k = 0; k < 4; k++) if (ks.sched[k]) q.radices.push_back(1u << ks.sched[k]);
 					q.noCollapse = true;
 				};
 				const int64_t sB = (int64_t)(n2 * n0); // stride of the middle factor's index inside T[m = i1*n2 + i2][k0]
@@ -1700,25 +1693,25 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 				p1.preOp = OP_BLUESTEIN_PRE; p1.auxOff2ForPre = chirpOff; p1.bsSwapIn = j.inverse; p1.opN = (uint32_t)N; p1.opStrideJ = (uint32_t)M1; p1.opStride0 = 1;
 				p1.postOp = OP_TWIDDLE_4STEP; p1.fsN = M; p1.fsColDiv = 1;
 				p1.inRole = j.inRole; p1.outRole = ROLE_TEMP; p1.label = "bluestein5-1";
-				setFast(p1, KERNEL_POW2_COL_BLUE, v1, bits1, tc1, th1);
+				setFast(p1, KERNEL_POW2_COL_BLUE, k1);
 				PassBuild p2 = b; // forward middle pass: FFT over i1, twiddle w_M1^(k1*i2), in place
 				p2.L = n1; p2.inStrideJ = p2.outStrideJ = sB; p2.colIn = p2.colOut = true;
 				p2.dims = withOthers({{n2 * n0, 1, 1}}, 1, 1);
 				p2.postOp = OP_TWIDDLE_4STEP; p2.fsN = M1; p2.fsColDiv = (uint32_t)n0;
 				p2.inRole = p2.outRole = ROLE_TEMP; p2.label = "bluestein5-2";
-				setFast(p2, KERNEL_POW2_COL, vb, bitsb, tcb, thb);
+				setFast(p2, KERNEL_POW2_COL, kb);
 				PassBuild p3 = b; // FFT over i2, * FFT(chirp)[k0 + n0*(k1 + n1*k2)], inverse FFT over k2, in place
 				p3.L = n2; p3.inStrideJ = p3.outStrideJ = (int64_t)n0; p3.colIn = p3.colOut = true;
 				p3.dims = withOthers({{n0, 1, 1}, {n1, sB, sB}}, 1, 1);
 				p3.midOp = OP_BLUESTEIN_MID; p3.aux2Off = bhatOff; p3.opStrideJ = (uint32_t)(n0 * n1); p3.opStride0 = 1; p3.opStride1 = (uint32_t)n0;
 				p3.inRole = p3.outRole = ROLE_TEMP; p3.label = "bluestein5-3";
-				setFast(p3, KERNEL_POW2_COL_BLUE, v3, bits3, tc3, th3);
+				setFast(p3, KERNEL_POW2_COL_BLUE, k3);
 				PassBuild p4 = b; // the middle pass backwards
 				p4.L = n1; p4.inStrideJ = p4.outStrideJ = sB; p4.colIn = p4.colOut = true;
 				p4.dims = withOthers({{n2 * n0, 1, 1}}, 1, 1);
 				p4.preOp = OP_FOURSTEP_INV_COL_PRE; p4.fsN = M1; p4.fsColDiv = (uint32_t)n0;
 				p4.inRole = p4.outRole = ROLE_TEMP; p4.label = "bluestein5-4";
-				setFast(p4, KERNEL_POW2_COL_BLUE, v4, bits4, tc4, th4);
+				setFast(p4, KERNEL_POW2_COL_BLUE, k4);
 				PassBuild p5 = b;
 				p5.L = n0; p5.inStrideJ = 1; p5.outStrideJ = (int64_t)M1; p5.colIn = p5.colOut = true;
 				p5.dims = withOthers({{M1, (int64_t)n0, 1}}, 1, 0);
@@ -1726,7 +1719,7 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 				p5.postOp = OP_BLUESTEIN_POST; p5.auxOff2ForPre = chirpOff; p5.bsSwapOut = j.inverse; p5.opN = (uint32_t)N; p5.opStrideJ = (uint32_t)M1; p5.opStride0 = 1;
 				p5.scale = j.scale;
 				p5.inRole = ROLE_TEMP; p5.outRole = j.outRole; p5.label = "bluestein5-5";
-				setFast(p5, KERNEL_POW2_COL_BLUE, v5, bits5, tc5, th5);
+				setFast(p5, KERNEL_POW2_COL_BLUE, k5);
 				for (PassBuild* q : {&p1, &p2, &p3, &p4, &p5}) { PassPlan pp; int r = finish_pass(*q, ar, pp); if (r) return r; passes.push_back(pp); }
 				out.uploadsPerAxis[j.axisIndex] = 5;
 				out.tempBytes = std::max<uint64_t>(out.tempBytes, nsub * M * es);
@@ -1778,10 +1771,9 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 	if (!unit && !d.disableFastKernels && j.N > 2048 && j.N <= singleCap && !j.others.empty() && j.others[0].inStride == 1 && j.others[0].outStride == 1) {
 		// a strided axis longer than the hand-specialised column kernels reach (2048): one pass would put ONE column in LDS per workgroup
 		// (uncoalesced 8-byte accesses, measured 0.4 TB/s on 4096 x 4096); two passes over tiles of neighbouring columns run at copy speed
-		int variant, bits[4], tc, thr, rad5[5], fpw;
 		const bool p2 = (j.N & (j.N - 1)) == 0;
 		std::vector<uint64_t> probe;
-		if (!(p2 && pow2_col_lookup(ilog2(j.N), dp, Switches::shape(d.sw.pow2ColShape, ilog2(j.N)), &variant, bits, &tc, &thr)) && !opfft_lookup(j.N, dp, true, false, 0, 0, &variant, rad5, &fpw, &thr) &&
+		if (!(p2 && pow2_col_lookup(ilog2(j.N), dp, Switches::shape(d.sw.pow2ColShape, ilog2(j.N)))) && !opfft_lookup(j.N, dp, true, false, 0, 0) &&
 		    choose_split(j.N, dp, d.maxLds, dmax, true, probe)) {
 			if (padded) return kPadUnsupported; // (two passes: no kernel of that plan skips elements)
 			singleCap = 2048;
@@ -1792,35 +1784,25 @@ static int plan_c2c_axis(const TransformDesc& d, const AxisJob& j, Arena& ar, Di
 	// (a power-of-two row beyond the interpreter's reach takes this branch only when its register-resident kernel is really there — table entry and 32-bit
 	// span —: otherwise the interpreter would be handed a row that does not fit LDS (error 3002) instead of the Four-Step plan below)
 	bool p2rowOK = false;
-	if (unit && !d.disableFastKernels && (j.N & (j.N - 1)) == 0 && j.N >= 4 && j.N <= (dp ? 8192u : (row15 ? 32768u : 16384u))) {
-		int variant, bits[4], fpw, thr;
-		const uint64_t rowPitch = j.others.empty() ? j.N : (uint64_t)std::max<int64_t>(std::llabs(j.others[0].inStride), std::llabs(j.others[0].outStride));
-		p2rowOK = (rowPitch * 64 + j.N) * (dp ? 16 : 8) < kSpanLimit && pow2_row_lookup(ilog2(j.N), dp, Switches::shape(d.sw.pow2RowShape, ilog2(j.N)), &variant, bits, &fpw, &thr, padded);
-	}
+	if (unit && !d.disableFastKernels && (j.N & (j.N - 1)) == 0 && j.N >= 4 && j.N <= (dp ? 8192u : (row15 ? 32768u : 16384u)))
+		p2rowOK = tile64_in_span(row_pitch(j.others, j.N), j.N, dp ? 16 : 8) && pow2_row_lookup(ilog2(j.N), dp, Switches::shape(d.sw.pow2RowShape, ilog2(j.N)), padded);
 	// ... and the hand-written long rows of the mixed-radix family (mixed_table_6.inc: 11^4, 5^6, 7^5 in ONE LDS buffer of 117-151 KB, one workgroup per CU): one pass where
 	// the Four-Step plan would take two (VKFFT_MI355X_LONGROWS=0: the fused Four-Step launch of kernel_mix_fused.h instead)
 	bool mixLongOK = false;
-	if (unit && !padded && !d.disableFastKernels && (j.N & (j.N - 1)) != 0 && j.N > singleCap && j.N <= (dp ? 8192u : 16807u) && d.sw.longRows != 0) {
-		int variant, rad5[5], fpw, thr;
-		const uint64_t rowPitch = j.others.empty() ? j.N : (uint64_t)std::max<int64_t>(std::llabs(j.others[0].inStride), std::llabs(j.others[0].outStride));
-		mixLongOK = (rowPitch * 64 + j.N) * (dp ? 16 : 8) < kSpanLimit && mixed_row_lookup(j.N, dp, &variant, rad5, &fpw, &thr);
-	}
+	if (unit && !padded && !d.disableFastKernels && (j.N & (j.N - 1)) != 0 && j.N > singleCap && j.N <= (dp ? 8192u : 16807u) && d.sw.longRows != 0)
+		mixLongOK = tile64_in_span(row_pitch(j.others, j.N), j.N, dp ? 16 : 8) && mixed_row_lookup(j.N, dp);
 	if (j.N <= singleCap || p2rowOK || mixLongOK) {
 		b.L = j.N;
 		if (unit && !padded && !d.disableFastKernels && ((j.N & (j.N - 1)) != 0 || j.N == 2)) { // curated non-power-of-two lengths (and N = 2): hand-specialised mixed-radix kernel
-			int variant, rad5[5], fpw, thr;
-			uint64_t rowPitch = j.others.empty() ? j.N : (uint64_t)std::max<int64_t>(std::llabs(j.others[0].inStride), std::llabs(j.others[0].outStride));
-			if ((rowPitch * 64 + j.N) * (dp ? 16 : 8) < kSpanLimit && mixed_row_lookup(j.N, dp, &variant, rad5, &fpw, &thr)) {
-				b.fastKernel = KERNEL_MIXED_ROW; b.fastVariant = variant; b.fastThreads = thr; b.forceT = (uint32_t)fpw;
-				for (int k = 0; k < 5; k++) if (rad5[k] > 1) b.radices.push_back((uint32_t)rad5[k]);
+			if (tile64_in_span(row_pitch(j.others, j.N), j.N, dp ? 16 : 8)) if (const KernelShape ks = mixed_row_lookup(j.N, dp)) {
+				b.fastKernel = KERNEL_MIXED_ROW; b.fastVariant = ks.variant; b.fastThreads = ks.threads; b.forceT = (uint32_t)ks.perWg;
+				for (int k = 0; k < 5; k++) if (ks.sched[k] > 1) b.radices.push_back((uint32_t)ks.sched[k]);
 			}
 		}
 		if (unit && !d.disableFastKernels && (j.N & (j.N - 1)) == 0 && j.N >= 4) {
-			int variant, bits[4], fpw, thr;
-			uint64_t rowPitch = j.others.empty() ? j.N : (uint64_t)std::max<int64_t>(std::llabs(j.others[0].inStride), std::llabs(j.others[0].outStride));
-			if ((rowPitch * 64 + j.N) * (dp ? 16 : 8) < kSpanLimit && pow2_row_lookup(ilog2(j.N), dp, Switches::shape(d.sw.pow2RowShape, ilog2(j.N)), &variant, bits, &fpw, &thr, padded)) {
-				b.fastKernel = KERNEL_POW2_ROW; b.fastVariant = variant; b.fastThreads = thr; b.forceT = (uint32_t)fpw;
-				for (int k = 0; k < 4; k++) if (bits[k]) b.radices.push_back(1u << bits[k]);
+			if (tile64_in_span(row_pitch(j.others, j.N), j.N, dp ? 16 : 8)) if (const KernelShape ks = pow2_row_lookup(ilog2(j.N), dp, Switches::shape(d.sw.pow2RowShape, ilog2(j.N)), padded)) {
+				b.fastKernel = KERNEL_POW2_ROW; b.fastVariant = ks.variant; b.fastThreads = ks.threads; b.forceT = (uint32_t)ks.perWg;
+				for (int k = 0; k < 4; k++) if (ks.sched[k]) b.radices.push_back(1u << ks.sched[k]);
 			}
 		}
 		b.inStrideJ = j.inStrideJ; b.outStrideJ = j.outStrideJ;
@@ -1910,9 +1892,8 @@ static bool real_row_prefers_bluestein(const Switches& sw, uint64_t L, bool dp) 
 	for (uint64_t q = 2; q * q <= rest; q++) while (rest % q == 0) { P = q; rest /= q; }
 	if (rest > 1) P = rest;
 	if (P <= 31) return false;
-	int v, r5[5], f, t; uint64_t len;
-	if (mixed_row_lookup(L, dp, &v, r5, &f, &t)) return false;
-	if (P == L) return !mixconv_lookup(true, false, P, dp, &v, &len, r5, &f, &t);
+	if (mixed_row_lookup(L, dp)) return false;
+	if (P == L) return !mixconv_lookup(true, false, P, dp);
 	MixradChoice mr;
 	return !mixrad_choose(sw, L, dp, true, mr);
 }
@@ -1992,19 +1973,18 @@ static uint64_t pairable_rows(const std::vector<HostDim>& others) {
 // a unit-stride fp32 row longer than the two-buffer single-pass limit that has one of the long instances of tools/gen_long_rows_table.py (one LDS buffer, one workgroup per CU)
 static bool long_row_instance(const TransformDesc& d, uint64_t L, bool dp) {
 	if (d.disableFastKernels || L <= max_row_len(dp, d.maxLds) || L > (dp ? 8192u : 16807u) || d.sw.longRows == 0) return false;
-	int v, r5[5], f, t;
-	return mixed_row_lookup(L, dp, &v, r5, &f, &t);
+	return (bool)mixed_row_lookup(L, dp);
 }
 static bool prefer_full_length_pairs(const TransformDesc& d, uint64_t N, bool unit, uint64_t rows, uint32_t preHalf, uint32_t postHalf, uint64_t halfLen) {
 	const int mode = d.sw.evenFull;
 	if (N > max_row_len(d.dp, d.maxLds)) return false; // (the long rows keep their half-length forms: one workgroup per CU is no place for twice the points)
 	if (!mode || d.disableFastKernels || !unit || rows < 2 || d.sw.noTmaps || d.sw.noRowPairs || d.sw.noMixedOps) return false;
-	int v, r5[5], f, t;
 	// (eight: the plain sides of R2C / C2R then move directly, kernel_mixed.h DIRECT; round 6: or the full length runs on the Rader-stage kernel, whose maps are the
 	// tables of the full-length forms only — the half-length complex form of 328 = 2 * 4 * 41 reals fell back to the interpreter: 0.17x the reference)
 	MixradChoice mr;
-	if (!(mixed_row_lookup(N, d.dp, &v, r5, &f, &t) && t / f >= 8) && !mixrad_choose(d.sw, N, d.dp, true, mr)) return false;
-	if (mode == 1 && opfft_lookup(halfLen, d.dp, false, false, preHalf, postHalf, &v, r5, &f, &t)) return false;
+	const KernelShape full = mixed_row_lookup(N, d.dp);
+	if (!(full && full.threads / full.perWg >= 8) && !mixrad_choose(d.sw, N, d.dp, true, mr)) return false;
+	if (mode == 1 && opfft_lookup(halfLen, d.dp, false, false, preHalf, postHalf)) return false;
 	return true;
 }
 static int plan_r2c_axis0_fused(const TransformDesc& d, bool inverse, const std::vector<HostDim>& othersReal, const std::vector<HostDim>& othersCplx,
@@ -2058,21 +2038,20 @@ static int plan_r2c_axis0_fused(const TransformDesc& d, bool inverse, const std:
 	}
 	b.L = even ? N / 2 : N;
 	uint64_t blueM = 0; // padded length of the Bluestein-wrapped full-length form (kernel_blue_r2r.h), 0: not used
-	int blueVariant = 0, blueBits[4] = {0, 0, 0, 0}, blueFpw = 0, blueThr = 0;
+	KernelShape blue;
 	if (padReal && (!is_supported_len(b.L, dmax) || b.L > max_row_len(dp, d.maxLds))) return kPadUnsupported;
 	bool blueByChoice = false; // the length is within the interpreter's reach, the fused Bluestein kernel is the faster form (real_row_prefers_bluestein)
 	if (is_supported_len(b.L, dmax) && !d.disableFastKernels && !padReal && real_row_prefers_bluestein(d.sw, b.L, dp) && !d.sw.noRealBlueChoice) {
-		uint64_t Mp = 64; while (Mp < 2 * N - 1) Mp *= 2;
+		const uint64_t Mp = blue_pow2_len(N, 64);
 		uint64_t pitch = N + 2;
 		if (!othersReal.empty()) pitch = (uint64_t)std::max<int64_t>(std::llabs(othersReal[0].inStride), 2 * std::llabs(othersCplx[0].inStride));
-		int v, bits[4], fpw, thr;
-		blueByChoice = Mp <= (dp ? 4096u : 8192u) && (pitch * 64 + 2 * N) * (dp ? 8 : 4) < kSpanLimit && pow2_blue_r2r_lookup(ilog2(Mp), dp, inverse ? OP_C2R_FULL : OP_R2C_FULL, &v, bits, &fpw, &thr);
+		blueByChoice = Mp <= (dp ? 4096u : 8192u) && tile64_in_span(pitch, 2 * N, dp ? 8 : 4) && pow2_blue_r2r_lookup(ilog2(Mp), dp, inverse ? OP_C2R_FULL : OP_R2C_FULL);
 	}
 	if (!is_supported_len(b.L, dmax) || blueByChoice) {
 		// the (half) length has a prime factor outside the radix / Rader stages: full-length "callback" form (real -> (x, 0),
 		// keep the first N/2+1 outputs; vkFFT_R2C.h:27) around a fused Bluestein transform of length N
 		if (d.disableFastKernels) return 3003;
-		uint64_t Mp = 64; while (Mp < 2 * N - 1) Mp *= 2;
+		const uint64_t Mp = blue_pow2_len(N, 64);
 		if (even && Mp > (dp ? 4096u : 8192u)) {
 			// long even rows: the full-length form would need a padded length of 16384 or more (one 128 KiB workgroup per CU, measured
 			// 0.24 TB/s at N = 5606).  Half-length complex transform of the packed pairs — whatever plan that length needs, here the fused
@@ -2106,8 +2085,9 @@ static int plan_r2c_axis0_fused(const TransformDesc& d, bool inverse, const std:
 		}
 		uint64_t pitch = N + 2;
 		if (!othersReal.empty()) pitch = (uint64_t)std::max<int64_t>(std::llabs(othersReal[0].inStride), 2 * std::llabs(othersCplx[0].inStride));
-		if ((pitch * 64 + 2 * N) * (dp ? 8 : 4) >= kSpanLimit) return 3003; // 32-bit buffer offsets inside a tile of rows
-		if (!pow2_blue_r2r_lookup(ilog2(Mp), dp, inverse ? OP_C2R_FULL : OP_R2C_FULL, &blueVariant, blueBits, &blueFpw, &blueThr)) return 3003;
+		if (!tile64_in_span(pitch, 2 * N, dp ? 8 : 4)) return 3003; // 32-bit buffer offsets inside a tile of rows
+		blue = pow2_blue_r2r_lookup(ilog2(Mp), dp, inverse ? OP_C2R_FULL : OP_R2C_FULL);
+		if (!blue) return 3003;
 		blueM = Mp; even = false; b.L = N;
 	}
 	// rows: combine the real-side and complex-side strides per dim
@@ -2188,8 +2168,8 @@ static int plan_r2c_axis0_fused(const TransformDesc& d, bool inverse, const std:
 		make_bluestein_tables(N, blueM, dp, ar, chirpOff, bhatOff, true);
 		b.L = blueM; b.blueN = (uint32_t)N;
 		b.midOp = OP_BLUESTEIN_MID; b.auxOff2ForPre = chirpOff;
-		b.fastKernel = KERNEL_POW2_BLUE_R2R; b.fastVariant = blueVariant; b.fastThreads = blueThr; b.forceT = (uint32_t)blueFpw;
-		for (int k = 0; k < 4; k++) if (blueBits[k]) b.radices.push_back(1u << blueBits[k]);
+		b.fastKernel = KERNEL_POW2_BLUE_R2R; b.fastVariant = blue.variant; b.fastThreads = blue.threads; b.forceT = (uint32_t)blue.perWg;
+		for (int k = 0; k < 4; k++) if (blue.sched[k]) b.radices.push_back(1u << blue.sched[k]);
 	}
 	PassPlan pp; int r = finish_pass(b, ar, pp); if (r) return r == 3002 ? 3003 : r;
 	passes.push_back(pp);
@@ -2257,8 +2237,7 @@ static int plan_r2r_axis_fused(const TransformDesc& d, int type, bool dst, uint6
 	case 1:
 		if (!dst) {
 			if (N < 2) return 3004;
-			int v, r5[5], f, t;
-			if (!d.disableFastKernels && N >= 5 && opfft_lookup(N - 1, dp, !unit, false, OP_DCT1H_PRE, OP_DCT1H_POST, &v, r5, &f, &t)) {
+			if (!d.disableFastKernels && N >= 5 && opfft_lookup(N - 1, dp, !unit, false, OP_DCT1H_PRE, OP_DCT1H_POST)) {
 				// half-length form on an ahead-of-time instance: complex FFT of N-1 points + the even R2C split (real parts only)
 				const uint64_t H = N - 1;
 				b.L = H; b.preOp = OP_DCT1H_PRE; b.postOp = OP_DCT1H_POST;
@@ -2327,11 +2306,9 @@ static int plan_r2r_axis_fused(const TransformDesc& d, int type, bool dst, uint6
 	bool blueByChoice = false; // within the interpreter's reach, but the fused Bluestein kernel is the faster form (real_row_prefers_bluestein)
 	if (is_supported_len(b.L, dmax) && unit && !d.disableFastKernels && real_row_prefers_bluestein(d.sw, b.L, dp) && !d.sw.noRealBlueChoice) {
 		const uint64_t Lb = (type == 2 || type == 3) ? N : b.L;
-		uint64_t Mp = 64; while (Mp < 2 * Lb - 1) Mp *= 2;
-		const uint64_t rowPitch = others.empty() ? N : (uint64_t)std::max<int64_t>(std::llabs(others[0].inStride), std::llabs(others[0].outStride));
+		const uint64_t Mp = blue_pow2_len(Lb, 64);
 		const uint32_t pre = type == 2 ? (uint32_t)OP_DCT2_PRE : type == 3 ? (uint32_t)OP_DCT3_PRE : b.preOp;
-		int v, bits[4], fpw, thr;
-		blueByChoice = Mp <= (dp ? 4096u : 8192u) && (rowPitch * 64 + 2 * N) * (dp ? 8 : 4) < kSpanLimit && pow2_blue_r2r_lookup(ilog2(Mp), dp, pre, &v, bits, &fpw, &thr);
+		blueByChoice = Mp <= (dp ? 4096u : 8192u) && tile64_in_span(row_pitch(others, N), 2 * N, dp ? 8 : 4) && pow2_blue_r2r_lookup(ilog2(Mp), dp, pre);
 	}
 	if (!is_supported_len(b.L, dmax) || blueByChoice) {
 		// the embedding length has a prime factor outside the radix / Rader stages (e.g. DST-I of 100: 202 = 2 * 101): the
@@ -2350,21 +2327,21 @@ static int plan_r2r_axis_fused(const TransformDesc& d, int type, bool dst, uint6
 				b.auxOff = aux;
 			}
 		}
-		uint64_t Mp = 64; while (Mp < 2 * Lb - 1) Mp *= 2;
+		const uint64_t Mp = blue_pow2_len(Lb, 64);
 		// The 16384-point instance with the DCT / DST-IV maps returns WRONG results on the device (relative error 0.5-0.9 at every odd length 4097 ... 8192 that reaches it;
 		// the emulator is right, and the same 16384 points with the DCT-II / III / I and R2C maps are right on both — found by tools/scan_device_parity.py in round 6, not
 		// root-caused: the instance is the one with 900 bytes of scratch).  Those lengths take the maps as passes around the complex plan instead (plan_real_by_maps).
 		if (type == 4 && !dp && Mp > 8192) return 3004;
-		int variant, bits[4], fpw, thr;
-		const uint64_t rowPitch = others.empty() ? N : (uint64_t)std::max<int64_t>(std::llabs(others[0].inStride), std::llabs(others[0].outStride));
-		if ((rowPitch * 64 + 2 * N) * (dp ? 8 : 4) >= kSpanLimit || !pow2_blue_r2r_lookup(ilog2(Mp), dp, b.preOp, &variant, bits, &fpw, &thr)) return 3004;
+		if (!tile64_in_span(row_pitch(others, N), 2 * N, dp ? 8 : 4)) return 3004;
+		const KernelShape ks = pow2_blue_r2r_lookup(ilog2(Mp), dp, b.preOp);
+		if (!ks) return 3004;
 		size_t chirpOff, bhatOff;
 		make_bluestein_tables(Lb, Mp, dp, ar, chirpOff, bhatOff, true); // aux / aux2 stay with the real transform's own tables
 		b.L = Mp; b.blueN = (uint32_t)Lb;
 		b.midOp = OP_BLUESTEIN_MID; b.auxOff2ForPre = chirpOff;
-		b.fastKernel = KERNEL_POW2_BLUE_R2R; b.fastVariant = variant; b.fastThreads = thr; b.forceT = (uint32_t)fpw;
+		b.fastKernel = KERNEL_POW2_BLUE_R2R; b.fastVariant = ks.variant; b.fastThreads = ks.threads; b.forceT = (uint32_t)ks.perWg;
 		b.radices.clear();
-		for (int k = 0; k < 4; k++) if (bits[k]) b.radices.push_back(1u << bits[k]);
+		for (int k = 0; k < 4; k++) if (ks.sched[k]) b.radices.push_back(1u << ks.sched[k]);
 	} else if (b.L > (unit ? max_row_len(dp, d.maxLds) : max_col_len(dp, d.maxLds, 1)) && !(unit && long_row_instance(d, b.L, dp))) {
 		// longer than one pass: the full-length form of the real transform through a multi-pass (Four-Step) complex FFT of the
 		// embedding length; the first load / last store apply the pre / post map to the row by natural index (the reference
@@ -2429,7 +2406,7 @@ int build_conv_axis_plan(const TransformDesc& d, const ConvAxisDesc& c, Directio
 	const uint64_t matrixCap = dp ? 256 : 512; // (beyond: 1024 threads per tile, 128 registers each — three systems do not fit)
 	uint64_t n0 = 1, M = L;
 	int mode = 6;
-	{ int v, b4[4], t, th; if (c.matrix > 1 && L == 2 * matrixCap && pow2_col_blue_lookup(ilog2(L), dp, 7, &v, b4, &t, &th)) mode = 7; } // (the narrow-tile instance)
+	if (c.matrix > 1 && L == 2 * matrixCap && pow2_col_blue_lookup(ilog2(L), dp, 7)) mode = 7; // (the narrow-tile instance)
 	if (L > 1024 || (c.matrix > 1 && L > matrixCap && mode == 6)) { // two factors, the inner one as large as a merged kernel allows
 		if (padded) return 3002; // (the passes of a split axis address by factor, not by the natural index the padded range is given in)
 		M = c.matrix > 1 ? matrixCap : 1024;
@@ -2437,8 +2414,8 @@ int build_conv_axis_plan(const TransformDesc& d, const ConvAxisDesc& c, Directio
 		n0 = L / M;
 		if (n0 < 64 || n0 > 1024 || M < 64) return 3002;
 	}
-	int variant, bits[4], tc, thr;
-	if (!pow2_col_blue_lookup(ilog2(M), dp, mode, &variant, bits, &tc, &thr)) return 3002;
+	const KernelShape ks = pow2_col_blue_lookup(ilog2(M), dp, mode);
+	if (!ks) return 3002;
 	const int64_t strideJ = (int64_t)d.bufStride[a - 1], sys = (int64_t)d.bufStride[nd - 1];
 	const uint64_t W = d.kind == 1 ? d.size[0] / 2 + 1 : d.size[0];
 	// buffer addressing: a column tile and every kernel system behind it lie within one 2 GiB resource
@@ -2475,11 +2452,11 @@ int build_conv_axis_plan(const TransformDesc& d, const ConvAxisDesc& c, Directio
 		for (int i = 0; i < 3; i++) q.dim[i] = {(uint32_t)dims[i].count, dims[i].inStride, dims[i].outStride};
 		q.convKerStride1 = kstr[1]; q.convKerStride2 = kstr[2]; q.convKerSysStride = sys;
 		q.convM = c.matrix; q.convCf = c.coordinates; q.convSymmetric = c.symmetric; q.convConj = c.conjugate;
-		q.tilesPerG0 = (uint32_t)((W + (uint64_t)tc - 1) / (uint64_t)tc);
+		q.tilesPerG0 = (uint32_t)((W + (uint64_t)ks.perWg - 1) / (uint64_t)ks.perWg);
 		q.scale = split ? 1.0 : c.scale;
 		if (padded) { q.padInL = q.padOutL = (uint32_t)d.padL[a]; q.padInN = q.padOutN = (uint32_t)(d.padR[a] - d.padL[a]); } // (spatial padding: read side of the forward half, write side of the inverse half)
-		pp.lutOff = build_pow2_stage_lut(ar, bits, dp);
-		pp.kernel = KERNEL_POW2_COL_BLUE; pp.variant = variant; pp.threads = (uint32_t)thr; pp.dp = dp; pp.auxIsKernel = true;
+		pp.lutOff = build_pow2_stage_lut(ar, ks.sched, dp);
+		pp.kernel = KERNEL_POW2_COL_BLUE; pp.variant = ks.variant; pp.threads = (uint32_t)ks.threads; pp.dp = dp; pp.auxIsKernel = true;
 		pp.inRole = pp.outRole = split ? ROLE_TEMP : ROLE_BUFFER; pp.inElemBytes = pp.outElemBytes = (int)es;
 		pp.label = "convolution";
 	}
@@ -2507,8 +2484,8 @@ int build_conv_axis_plan(const TransformDesc& d, const ConvAxisDesc& c, Directio
 	}
 	out.passes.push_back(pp);
 	{ // ---- pass A backwards (pow2_col_blue_kernel MODE 8): scratch -> data, conj twiddle, inverse FFT over k0, normalisation
-		int v8, b8[4], tc8, thr8;
-		if (!pow2_col_blue_lookup(ilog2(n0), dp, 8, &v8, b8, &tc8, &thr8)) return 3002;
+		const KernelShape k8 = pow2_col_blue_lookup(ilog2(n0), dp, 8);
+		if (!k8) return 3002;
 		PassPlan pc; memset(&pc.prm, 0, sizeof(pc.prm));
 		PassParams& q = pc.prm;
 		q.L = (uint32_t)n0; q.inStrideJ = (int64_t)M * tRow; q.outStrideJ = (int64_t)M * strideJ;
@@ -2523,7 +2500,7 @@ int build_conv_axis_plan(const TransformDesc& d, const ConvAxisDesc& c, Directio
 		while (dims.size() > 3) { pc.hostLoop.push_back(dims.back()); dims.pop_back(); }
 		for (int i = 0; i < 3; i++) q.dim[i] = {(uint32_t)dims[i].count, dims[i].inStride, dims[i].outStride};
 		q.fsN = (uint32_t)L; q.fsColFromDim1 = 1; q.scale = c.scale;
-		q.tilesPerG0 = (uint32_t)((W + (uint64_t)tc8 - 1) / (uint64_t)tc8);
+		q.tilesPerG0 = (uint32_t)((W + (uint64_t)k8.perWg - 1) / (uint64_t)k8.perWg);
 		{ // two-level Four-Step table of w_L (as finish_pass builds it)
 			const uint32_t lo = (ceil_log2(L) + 1) / 2;
 			const uint64_t nlo = 1ull << lo, nhi = (L + nlo - 1) / nlo;
@@ -2532,8 +2509,8 @@ int build_conv_axis_plan(const TransformDesc& d, const ConvAxisDesc& c, Directio
 			for (uint64_t i = 0; i < nhi; i++) ar.putc(off, nlo + i, unit_root(i * nlo, L), dp);
 			q.fsLoBits = lo; pc.auxOff = off;
 		}
-		pc.lutOff = build_pow2_stage_lut(ar, b8, dp);
-		pc.kernel = KERNEL_POW2_COL_BLUE; pc.variant = v8; pc.threads = (uint32_t)thr8; pc.dp = dp;
+		pc.lutOff = build_pow2_stage_lut(ar, k8.sched, dp);
+		pc.kernel = KERNEL_POW2_COL_BLUE; pc.variant = k8.variant; pc.threads = (uint32_t)k8.threads; pc.dp = dp;
 		pc.inRole = ROLE_TEMP; pc.outRole = ROLE_BUFFER; pc.inElemBytes = pc.outElemBytes = (int)es;
 		pc.label = "convolution-A-back";
 		out.passes.push_back(pc);
