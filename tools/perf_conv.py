@@ -1,7 +1,8 @@
 """Convolution throughput next to the reference on the same box (same call): python tools/perf_conv.py  ->  JSON lines.
 Algorithmic bytes of one convolution append = read + write of the data systems + one read of the kernel systems.
-python tools/perf_conv.py rows: one-dimensional plans, the one-launch form (pow2_conv_row_kernel) against VKFFT_MI355X_CONV_SEPARATE=1 (three launches) in the same
-process, alternating, on one buffer of 256 MiB."""
+python tools/perf_conv.py rows: one-dimensional plans, the one-launch form (pow2_conv_row_kernel, mix_conv_row_kernel) against VKFFT_MI355X_CONV_SEPARATE=1 (three
+launches) in the same process, alternating, on one buffer of 256 MiB; beside them the plain transform of the same rows (forward and normalised inverse in turn): the
+ceiling of a kernel that reads and writes the data once."""
 import ctypes as C, json, os, sys, time
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, root)
@@ -28,15 +29,20 @@ def rows_ab(n, dp, r2c, pad, mib=256, rounds=7, it=10):
     finally:
         del os.environ["VKFFT_MI355X_CONV_SEPARATE"]
     info = {k: a.launch_info() for k, a in apps.items()}
-    for a in apps.values():
-        for _ in range(3): a.forward()
+    apps["plain"] = api.App([n], rows, buffer_ptr=data.data_ptr(), dp=dp, r2c=r2c, normalize=True)  # (no padding: the whole rows)
+    plain_kernel = apps["plain"].launch_info()[1]
+    def run(k, a, i):
+        if k == "plain" and i % 2: a.inverse()
+        else: a.forward()
+    for k, a in apps.items():
+        for i in range(4): run(k, a, i)
     torch.cuda.synchronize()
     ms = {k: [] for k in apps}
     for _ in range(rounds):
         for k, a in apps.items():
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            for _ in range(it): a.forward()
+            for i in range(it): run(k, a, i)
             e1.record(); torch.cuda.synchronize()
             ms[k].append(e0.elapsed_time(e1) / it)
     for a in apps.values(): a.delete()
@@ -45,13 +51,19 @@ def rows_ab(n, dp, r2c, pad, mib=256, rounds=7, it=10):
     return dict(n=n, dp=dp, r2c=r2c, zero_padded_upper_half=bool(pad), rows=rows, launches={k: v[0] for k, v in info.items()}, kernel=info["fused"][1],
                 ms={k: round(v, 4) for k, v in med.items()}, ms_min_max={k: [round(min(v), 4), round(max(v), 4)] for k, v in ms.items()},
                 fused_alg_GBps=round(moved / med["fused"] / 1e6, 1), separate_alg_GBps=round(moved / med["separate"] / 1e6, 1),
-                speedup=round(med["separate"] / med["fused"], 3))
+                plain_kernel=plain_kernel, plain_GBps=round(2 * rows * rb / med["plain"] / 1e6, 1),
+                speedup=round(med["separate"] / med["fused"], 3), separate_spread=round((max(ms["separate"]) - min(ms["separate"])) / med["separate"], 3))
 
 
 if len(sys.argv) > 1 and sys.argv[1] == "rows":
     print(json.dumps(dict(source_hash=api.source_hash(), library_is_current=api.library_is_current(), device=torch.cuda.get_device_name(0))), flush=True)
     for n, dp, r2c, pad in [(256, False, False, False), (1024, False, False, False), (4096, False, False, False), (256, False, True, False), (1024, False, True, False),
-                            (4096, False, True, False), (1024, True, False, False), (1024, True, True, False), (1024, False, False, True), (4096, False, True, True)]:
+                            (4096, False, True, False), (1024, True, False, False), (1024, True, True, False), (1024, False, False, True), (4096, False, True, True),
+                            # 7-smooth rows (mix_conv_row_kernel): the short ones move their tile as one contiguous run, the others load and store in the transforms
+                            (100, False, False, False), (200, False, False, False), (360, False, False, False), (1000, False, False, False), (3000, False, False, False),
+                            (4000, False, False, False), (100, False, True, False), (360, False, True, False), (1000, False, True, False), (3000, False, True, False),
+                            (4000, False, True, False), (100, True, False, False), (1000, True, False, False), (100, True, True, False), (1000, True, True, False),
+                            (4000, False, False, True), (4000, False, True, True)]:
         print(json.dumps(rows_ab(n, dp, r2c, pad)), flush=True)
     sys.exit(0)
 ref = None

@@ -33,7 +33,7 @@ struct AppState {
 	                               // convFwd / convInv then omit the axis (planner.cpp build_conv_axis_plan)
 	VkFFTApplication* convInvFull = nullptr; // merged form only: VkFFTAppend(app, 1) is a plain inverse over ALL axes; convInv lacks the merged one, so that
 	VkFFTConfiguration convInvFullCfg = {};  // direction gets its own application, created at its first use from this configuration
-	bool convRow = false;          // one-dimensional plan in ONE launch (pow2_conv_row_kernel): convMid is the whole convolution, there is no convFwd, and convInv —
+	bool convRow = false;          // one-dimensional plan in ONE launch (pow2_conv_row_kernel / mix_conv_row_kernel): convMid is the whole convolution, there is no convFwd, and convInv —
 	                               // a plain inverse over the axis, built at plan creation — serves VkFFTAppend(app, 1) only
 	uint32_t zeroPadMask = 0;      // zero-padded axes whose plan cannot skip the range: it is written with zeros ahead of the transform that reads it
 };
@@ -124,7 +124,7 @@ VKFFT_API int vkfftMI355XDescribePlan(const VkFFTApplication* app, int inverse, 
 	const AppState* st = (const AppState*)app->impl;
 	if (st && (st->convFwd || st->convRow)) {
 		if (st->convRow && inverse != 1) { // the whole convolution is one launch
-			if (names && cap) snprintf(names, (size_t)cap, "pow2_conv_row_kernel");
+			if (names && cap) snprintf(names, (size_t)cap, "%s", kernel_kind_name(((const DirectionPlan*)st->convMid->impl)->passes[0].kernel).global);
 			return 1;
 		}
 		// convolution application: what VkFFTAppend(app, -1) launches — forward transform (without the merged axis), the merged axis or the separate
@@ -565,8 +565,9 @@ VkFFTResult initialize_convolution(VkFFTApplication* app, const VkFFTConfigurati
 			} else free_direction(pl);
 		} else { free(pl); delete dpl; }
 	}
-	// one-dimensional plan: the whole convolution in one launch of pow2_conv_row_kernel (kernel_pow2_conv.h) when an instance serves the row — dense rows of a
-	// power-of-two length in the buffer itself, every coordinate with its own kernel component, one kernel set.  Everything else keeps the three launches
+	// one-dimensional plan: the whole convolution in one launch of pow2_conv_row_kernel (kernel_pow2_conv.h) or mix_conv_row_kernel (kernel_mix_conv.h) when an
+	// instance serves the row — dense rows of a power-of-two length, or of a 7-smooth one of 100 ... 4096 points, in the buffer itself, every coordinate with its
+	// own kernel component, one kernel set.  Everything else keeps the three launches
 	// (VKFFT_MI355X_CONV_SEPARATE selects them here too)
 	if (in.FFTdim == 1 && m <= 1 && nk == 1 && !in.crossPowerSpectrumNormalization && !in.frequencyZeroPadding && !in.isInputFormatted && !sw.convSeparate &&
 	    !(in.performR2C && in.conjugateConvolution) && in.size[0] > 1) {
@@ -589,7 +590,7 @@ VkFFTResult initialize_convolution(VkFFTApplication* app, const VkFFTConfigurati
 			if (build_conv_row_plan(d, cd, *dpl) == 0 && !dpl->arena.empty() && hipMalloc(&dpl->dArena, dpl->arena.size()) == hipSuccess &&
 			    hipMemcpy(dpl->dArena, dpl->arena.data(), dpl->arena.size(), hipMemcpyHostToDevice) == hipSuccess) {
 				st->convMid = pl; st->convRow = true;
-				if (in.printMemoryLayout || sw.printPlan) fprintf(stderr, "[vkfft_mi355x] convolution: axis 0 merged (forward, kernel product, inverse in one launch of pow2_conv_row_kernel, %u rows per workgroup%s)\n", dpl->passes[0].prm.T, in.performR2C ? ", two real rows per transform" : "");
+				if (in.printMemoryLayout || sw.printPlan) fprintf(stderr, "[vkfft_mi355x] convolution: axis 0 merged (forward, kernel product, inverse in one launch of %s, %u rows per workgroup%s)\n", kernel_kind_name(dpl->passes[0].kernel).global, dpl->passes[0].prm.T, in.performR2C ? ", two real rows per transform" : "");
 			} else free_direction(pl);
 		} else { free(pl); delete dpl; }
 	}

@@ -5,6 +5,7 @@
 #include "kernel_opfft.h"
 #include "kernel_mixed.h"
 #include "kernel_mixconv.h"
+#include "kernel_mix_conv.h"
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -30,6 +31,8 @@ int launch_pass(const PassPlan& pp, const PassParams& prm, hipStream_t stream) {
 		return launch_pow2_col_blue(pp, prm, stream);
 	case KERNEL_POW2_CONV_ROW:
 		return launch_pow2_conv_row(pp, prm, stream);
+	case KERNEL_MIX_CONV_ROW:
+		return launch_mix_conv_row(pp, prm, stream);
 	case KERNEL_TRANSPOSE:
 		return launch_transpose(pp, prm, stream);
 	case KERNEL_REAL_MAP:
@@ -170,6 +173,33 @@ int launch_mixconv(const PassPlan& pp, const PassParams& prm, hipStream_t stream
 	return launch_on_grid((uint64_t)prm.tilesPerG0 * (prm.colMerge ? 1u : prm.dim[1].count) * prm.dim[2].count, fn, prm, stream);
 }
 
+// ---- one-launch convolution on 7-smooth rows: eight table parts (kernels_mixconv_rows_*.hip) ------------------------
+#define VKFFT_MIX_CONV_ROWS_PARTS(X, V, f) X(V, f, 0) X(V, f, 1) X(V, f, 2) X(V, f, 3) X(V, f, 4) X(V, f, 5) X(V, f, 6) X(V, f, 7)
+VKFFT_REGISTRY_PARTS(MixConvRowVariant, mix_conv_rows, kMixConvRowsParts, VKFFT_MIX_CONV_ROWS_PARTS)
+static const MixConvRowVariant* mix_conv_rows_part(int part, int* count) {
+	return part < 0 ? nullptr : mix_conv_rows_part_fns[part % kMixConvRowsParts](count);
+}
+KernelShape mix_conv_row_lookup(uint64_t n, bool dp, bool real) {
+	for (int part = 0; part < kMixConvRowsParts; part++) {
+		int cnt = 0;
+		const MixConvRowVariant* tab = mix_conv_rows_part(part, &cnt);
+		for (int i = 0; i < cnt; i++) {
+			if ((uint64_t)tab[i].n != n || tab[i].dp != dp || tab[i].real != real) continue;
+			KernelShape k;
+			k.variant = (part << 16) | i; k.perWg = tab[i].fpw; k.threads = tab[i].tpf * tab[i].fpw;
+			for (int r = 0; r < 5; r++) k.sched[r] = tab[i].rad[r];
+			return k;
+		}
+	}
+	return {};
+}
+int launch_mix_conv_row(const PassPlan& pp, const PassParams& prm, hipStream_t stream) {
+	int cnt = 0;
+	const MixConvRowVariant* tab = mix_conv_rows_part((pp.variant >> 16) % kMixConvRowsParts, &cnt);
+	const int idx = pp.variant & 0xffff;
+	return launch_on_grid((uint64_t)prm.tilesPerG0, pp.variant >= 0 && idx < cnt ? tab[idx].launch : nullptr, prm, stream);
+}
+
 // ---- op-FFT registry: nine table parts, one translation unit each (kernels_opfft_*.hip) ---------------------------
 #define VKFFT_OPFFT_PARTS(X, V, f) X(V, f, f32_row_0) X(V, f, f32_row_1) X(V, f, f32_col_0) X(V, f, f32_col_1) X(V, f, f64_row_0) X(V, f, f64_row_1) X(V, f, f64_col_0) X(V, f, f64_col_1) \
 	X(V, f, f32_col_2) /* part 8: tools/gen_opfft_col_extra.py */
@@ -181,6 +211,7 @@ static const OpfftVariant* opfft_part(int part, int* count) { // part = 2 * ((dp
 #undef VKFFT_PART_REF
 #undef VKFFT_PART_DECL
 #undef VKFFT_OPFFT_PARTS
+#undef VKFFT_MIX_CONV_ROWS_PARTS
 #undef VKFFT_MIXCONV_PARTS
 #undef VKFFT_MIXED_PARTS
 static uint32_t opfft_family(uint32_t op) { // DST members run on the DCT instance of their family

@@ -2521,19 +2521,26 @@ int build_conv_axis_plan(const TransformDesc& d, const ConvAxisDesc& c, Directio
 }
 
 // ---- one-launch convolution of a one-dimensional plan -----------------------------------------------------------
-// Unit-stride power-of-two rows with an instance of pow2_conv_row_kernel (kernel_pow2_conv.h): rows b * cf + v of the dense in-place layout, every one
-// multiplied with kernel system v.  C2C: one row per slot; R2C: a slot is the pair of real rows (2 q cf + v, (2 q + 1) cf + v).
+// Unit-stride rows with an instance of pow2_conv_row_kernel (kernel_pow2_conv.h, powers of two) or of mix_conv_row_kernel (kernel_mix_conv.h, 7-smooth lengths
+// of 100 ... 4096 points; R2C: even ones): rows b * cf + v of the dense in-place layout, every one multiplied with kernel system v.  C2C: one row per slot;
+// R2C: a slot is the pair of real rows (2 q cf + v, (2 q + 1) cf + v).
 int build_conv_row_plan(const TransformDesc& d, const ConvAxisDesc& c, DirectionPlan& out) {
 	out = DirectionPlan();
 	Arena ar(out.arena);
 	if (d.fftDim != 1 || d.kind > 1 || d.omit[0] || d.padFrequency || d.disableFastKernels || d.inFormatted || d.outFormatted) return 3002;
 	const uint64_t N = d.size[0];
-	if (N < 2 || (N & (N - 1)) != 0 || c.matrix > 1 || c.coordinates < 1) return 3002;
-	const bool dp = d.dp, real = d.kind == 1;
+	if (N < 2 || c.matrix > 1 || c.coordinates < 1) return 3002;
+	const bool dp = d.dp, real = d.kind == 1, pow2 = (N & (N - 1)) == 0;
 	if (real && c.conjugate != 0) return 3002; // (conj of one operand is not linear over the a + i b pairing)
 	if (c.conjugate > 2) return 3002;
 	int variant, bits[4], fpw, thr;
-	if (!pow2_conv_row_lookup(ilog2(N), dp, real, &variant, bits, &fpw, &thr)) return 3002;
+	KernelShape mix; // (the table holds no odd length for pairs of real rows)
+	if (pow2) {
+		if (!pow2_conv_row_lookup(ilog2(N), dp, real, &variant, bits, &fpw, &thr)) return 3002;
+	} else {
+		if (!(mix = mix_conv_row_lookup(N, dp, real))) return 3002;
+		variant = mix.variant; fpw = mix.perWg; thr = mix.threads;
+	}
 	const uint64_t es = dp ? 16 : 8, cf = c.coordinates;
 	const uint64_t pitch = real ? N + 2 : N, kerSys = real ? N / 2 + 1 : N; // reals resp. complex elements per data row; complex elements per kernel system
 	if (d.bufStride[0] != kerSys) return 3002; // dense rows only
@@ -2554,8 +2561,8 @@ int build_conv_row_plan(const TransformDesc& d, const ConvAxisDesc& c, Direction
 	q.scale = c.scale;
 	if (d.padR[0] > N) return 3002;
 	if (d.padR[0] > d.padL[0]) { q.padInL = q.padOutL = (uint32_t)d.padL[0]; q.padInN = q.padOutN = (uint32_t)(d.padR[0] - d.padL[0]); }
-	pp.lutOff = build_pow2_stage_lut(ar, bits, dp);
-	pp.kernel = KERNEL_POW2_CONV_ROW; pp.variant = variant; pp.threads = (uint32_t)thr; pp.dp = dp; pp.auxIsKernel = true;
+	pp.lutOff = pow2 ? build_pow2_stage_lut(ar, bits, dp) : build_mix_stage_lut(ar, mix.sched, dp);
+	pp.kernel = pow2 ? KERNEL_POW2_CONV_ROW : KERNEL_MIX_CONV_ROW; pp.variant = variant; pp.threads = (uint32_t)thr; pp.dp = dp; pp.auxIsKernel = true;
 	pp.inRole = pp.outRole = ROLE_BUFFER; pp.inElemBytes = pp.outElemBytes = (int)(real ? es / 2 : es);
 	pp.label = "convolution";
 	out.passes.push_back(pp);
