@@ -2,7 +2,9 @@
 Algorithmic bytes of one convolution append = read + write of the data systems + one read of the kernel systems.
 python tools/perf_conv.py rows: one-dimensional plans, the one-launch form (pow2_conv_row_kernel, mix_conv_row_kernel) against VKFFT_MI355X_CONV_SEPARATE=1 (three
 launches) in the same process, alternating, on one buffer of 256 MiB; beside them the plain transform of the same rows (forward and normalised inverse in turn): the
-ceiling of a kernel that reads and writes the data once."""
+ceiling of a kernel that reads and writes the data once.
+python tools/perf_conv.py planes: 2-D / 3-D plans whose last axis is 7-smooth and no power of two, the merged last axis (mix_conv_col_kernel: three launches for a
+2-D plan) against VKFFT_MI355X_CONV_SEPARATE=1 (five) in the same process, alternating, on the same buffer."""
 import ctypes as C, json, os, sys, time
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, root)
@@ -55,6 +57,57 @@ def rows_ab(n, dp, r2c, pad, mib=256, rounds=7, it=10):
                 speedup=round(med["separate"] / med["fused"], 3), separate_spread=round((max(ms["separate"]) - min(ms["separate"])) / med["separate"], 3))
 
 
+def planes_ab(shape, dp, r2c, pad, mib=256, rounds=7, it=10):
+    """merged last axis against separate passes, timed like rows_ab.  shape: axis 0 first, the merged axis last; as many batches as fit `mib` (at least one)"""
+    es = 16 if dp else 8
+    elems = (shape[0] // 2 + 1 if r2c else shape[0]) * int(np.prod(shape[1:]))
+    nb = max(1, (mib << 20) // (elems * es))
+    rt = torch.float64 if dp else torch.float32
+    data = torch.rand(2 * elems * nb, device="cuda", dtype=rt)
+    kern = torch.zeros(2 * elems, device="cuda", dtype=rt); kern[0::2] = 1
+    kw = dict(buffer_ptr=data.data_ptr(), kernel=kern.data_ptr(), performConvolution=1, dp=dp, r2c=r2c, normalize=True)
+    last = len(shape) - 1
+    if pad:
+        flag = [0] * 4; left = [0] * 4; right = [0] * 4
+        flag[last], left[last], right[last] = 1, shape[last] // 2, shape[last]
+        kw.update(performZeropadding=flag, fft_zeropad_left=left, fft_zeropad_right=right)
+    apps = {}
+    apps["merged"] = api.App(list(shape), nb, **kw)
+    os.environ["VKFFT_MI355X_CONV_SEPARATE"] = "1"
+    try:
+        apps["separate"] = api.App(list(shape), nb, **kw)
+    finally:
+        del os.environ["VKFFT_MI355X_CONV_SEPARATE"]
+    info = {k: a.launch_info() for k, a in apps.items()}
+    buf = C.create_string_buffer(2048)
+    apps["merged"].lib.vkfftMI355XDescribePlan(C.byref(apps["merged"].app), 0, buf, 2048)
+    names = sorted(set(x.split("<")[0] for x in buf.value.decode().split(",") if x))
+    for a in apps.values():
+        for i in range(4): a.forward()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in apps}
+    for _ in range(rounds):
+        for k, a in apps.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(it): a.forward()
+            e1.record(); torch.cuda.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / it)
+    for a in apps.values(): a.delete()
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    moved = 2 * nb * elems * es  # one read and one write of the data (the padded half included: the other axes visit it)
+    return dict(shape=list(shape), dp=dp, r2c=r2c, zero_padded_upper_half_of_last_axis=bool(pad), batches=nb, launches={k: v[0] for k, v in info.items()}, merged_kernels=names,
+                ms={k: round(v, 4) for k, v in med.items()}, ms_min_max={k: [round(min(v), 4), round(max(v), 4)] for k, v in ms.items()},
+                merged_alg_GBps=round(moved / med["merged"] / 1e6, 1), separate_alg_GBps=round(moved / med["separate"] / 1e6, 1),
+                speedup=round(med["separate"] / med["merged"], 3), separate_spread=round((max(ms["separate"]) - min(ms["separate"])) / med["separate"], 3))
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "planes":
+    print(json.dumps(dict(source_hash=api.source_hash(), library_is_current=api.library_is_current(), device=torch.cuda.get_device_name(0))), flush=True)
+    for shape, dp, r2c, pad in [((1920, 1080), False, False, False), ((1000, 1000), False, False, False), ((360, 360, 360), False, False, False), ((360, 360, 360), False, True, False),
+                                ((1024, 1536), False, False, False), ((480, 500), True, False, False), ((1920, 1080), False, False, True)]:
+        print(json.dumps(planes_ab(shape, dp, r2c, pad)), flush=True)
+    sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "rows":
     print(json.dumps(dict(source_hash=api.source_hash(), library_is_current=api.library_is_current(), device=torch.cuda.get_device_name(0))), flush=True)
     for n, dp, r2c, pad in [(256, False, False, False), (1024, False, False, False), (4096, False, False, False), (256, False, True, False), (1024, False, True, False),

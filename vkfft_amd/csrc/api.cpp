@@ -561,7 +561,7 @@ VkFFTResult initialize_convolution(VkFFTApplication* app, const VkFFTConfigurati
 				st->convMid = pl;
 				st->convInvFullCfg = b;
 				f.omitDimension[in.FFTdim - 1] = 1; b.omitDimension[in.FFTdim - 1] = 1;
-				if (in.printMemoryLayout || sw.printPlan) fprintf(stderr, "[vkfft_mi355x] convolution: axis %d merged (forward, %ux%u kernel product, inverse in one pass of pow2_col_blue_kernel)\n", (int)in.FFTdim - 1, cd.matrix, cd.matrix);
+				if (in.printMemoryLayout || sw.printPlan) fprintf(stderr, "[vkfft_mi355x] convolution: axis %d merged (forward, %ux%u kernel product, inverse in one pass of %s)\n", (int)in.FFTdim - 1, cd.matrix, cd.matrix, kernel_kind_name(dpl->passes[dpl->passes.size() / 2].kernel).global);
 			} else free_direction(pl);
 		} else { free(pl); delete dpl; }
 	}

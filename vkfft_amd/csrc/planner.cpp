@@ -2393,16 +2393,69 @@ static int plan_r2r_axis_fused(const TransformDesc& d, int type, bool dst, uint6
 // factors n0 x M) take three passes instead of the five of "two forward passes, product, two inverse passes": the forward first pass A (FFT over n0,
 // Four-Step twiddle, data -> scratch), the merged pass on the inner factor M (its outputs k1 of column k0 are the frequencies k0 + n0 k1 of the
 // kernel) in place in the scratch, and pass A run backwards (scratch -> data) — the shape of the multi-pass Bluestein plan (MODE 1 / 2 / 3).
+// A 7-smooth last axis that is no power of two, 12 ... 2048 points (fp64: ... 512): ONE pass of mix_conv_col_kernel (kernel_mix_conv_col.h) where the table holds
+// the length.  No kernel matrix and no split (two-factor) form: such plans keep the separate passes.  The dims are laid out as the non-split power-of-two form
+// lays them — columns, the other spatial dimension, systems — but the systems b * cf + v are ONE dimension (dim[2]; the kernel takes v = index mod cf): the
+// kernel pointer depends on the coordinate, so only a batch without coordinates may go to the host loop, which advances the data alone.
+static int build_conv_axis_mixed(const TransformDesc& d, const ConvAxisDesc& c, Arena& ar, DirectionPlan& out) {
+	const int nd = d.fftDim, a = nd - 1;
+	const uint64_t L = d.size[a];
+	const bool dp = d.dp;
+	const uint64_t es = dp ? 16 : 8;
+	if (c.matrix > 1 || c.coordinates < 1 || c.conjugate > 2) return 3002;
+	const KernelShape ks = mix_conv_col_lookup(L, dp);
+	if (!ks) return 3002;
+	const int64_t strideJ = (int64_t)d.bufStride[a - 1], sys = (int64_t)d.bufStride[nd - 1];
+	const uint64_t W = d.kind == 1 ? d.size[0] / 2 + 1 : d.size[0];
+	const uint64_t cf = c.coordinates, systems = d.batch * cf;
+	if (systems == 0 || systems >= (1ull << 31)) return 3002;
+	// buffer addressing: a column tile and every kernel system behind it lie within one 2 GiB resource
+	if (((uint64_t)L * (uint64_t)strideJ + 64) * es + c.kernelSystems * (uint64_t)sys * es >= kSpanLimit) return 3002;
+	if (d.padR[a] > L) return 3002;
+	std::vector<HostDim> spatial; // strides in the data buffer (and in the kernel buffer: one kernel system is laid out as one data system)
+	for (int o = 1; o < a; o++) spatial.push_back({d.size[o], (int64_t)d.bufStride[o - 1], (int64_t)d.bufStride[o - 1]});
+	if (spatial.size() > 2 || (spatial.size() == 2 && cf > 1)) return 3002;
+	PassPlan pp; memset(&pp.prm, 0, sizeof(pp.prm));
+	PassParams& q = pp.prm;
+	q.L = (uint32_t)L;
+	q.inStrideJ = q.outStrideJ = strideJ; q.convKerStrideJ = strideJ;
+	q.dim[0] = {(uint32_t)W, 1, 1};
+	if (spatial.size() == 2) { // four dimensions: both spatial ones in the grid, the batch (no coordinates: one kernel system) on the host
+		q.dim[1] = {(uint32_t)spatial[0].count, spatial[0].inStride, spatial[0].inStride}; q.convKerStride1 = spatial[0].inStride;
+		q.dim[2] = {(uint32_t)spatial[1].count, spatial[1].inStride, spatial[1].inStride}; q.convKerStride2 = spatial[1].inStride;
+		if (d.batch > 1) pp.hostLoop.push_back({d.batch, sys, sys});
+	} else {
+		if (spatial.size() == 1) { q.dim[1] = {(uint32_t)spatial[0].count, spatial[0].inStride, spatial[0].inStride}; q.convKerStride1 = spatial[0].inStride; }
+		else q.dim[1] = {1, 0, 0};
+		q.dim[2] = {(uint32_t)systems, sys, sys}; q.convKerStride2 = 0;
+	}
+	q.convKerSysStride = sys; q.convSysStride = sys;
+	q.convM = 1; q.convCf = spatial.size() == 2 ? 1u : (uint32_t)cf; q.convConj = c.conjugate;
+	q.T = (uint32_t)ks.perWg;
+	q.tilesPerG0 = (uint32_t)((W + (uint64_t)ks.perWg - 1) / (uint64_t)ks.perWg);
+	if ((uint64_t)q.tilesPerG0 * q.dim[1].count * q.dim[2].count > 0x7fffffffull) return 3002;
+	q.scale = c.scale;
+	if (d.padR[a] > d.padL[a]) { q.padInL = q.padOutL = (uint32_t)d.padL[a]; q.padInN = q.padOutN = (uint32_t)(d.padR[a] - d.padL[a]); }
+	pp.lutOff = build_mix_stage_lut(ar, ks.sched, dp);
+	pp.kernel = KERNEL_MIX_CONV_COL; pp.variant = ks.variant; pp.threads = (uint32_t)ks.threads; pp.dp = dp; pp.auxIsKernel = true;
+	pp.inRole = pp.outRole = ROLE_BUFFER; pp.inElemBytes = pp.outElemBytes = (int)es;
+	pp.label = "convolution";
+	out.passes.push_back(pp);
+	out.uploadsPerAxis[a] = 1;
+	return 0;
+}
+
 int build_conv_axis_plan(const TransformDesc& d, const ConvAxisDesc& c, DirectionPlan& out) {
 	out = DirectionPlan();
 	Arena ar(out.arena);
 	const int nd = d.fftDim, a = nd - 1;
 	if (nd < 2 || d.kind > 1 || d.omit[a] || d.padFrequency || d.disableFastKernels || d.inFormatted || d.outFormatted) return 3002;
 	const uint64_t L = d.size[a];
-	if ((L & (L - 1)) != 0 || c.coordinates > 3 || c.coordinates < 1 || (c.matrix > 1 && c.matrix != c.coordinates)) return 3002;
 	const bool dp = d.dp;
 	const uint64_t es = dp ? 16 : 8;
 	const bool padded = d.padR[a] > d.padL[a];
+	if ((L & (L - 1)) != 0) return build_conv_axis_mixed(d, c, ar, out);
+	if (c.coordinates > 3 || c.coordinates < 1 || (c.matrix > 1 && c.matrix != c.coordinates)) return 3002;
 	const uint64_t matrixCap = dp ? 256 : 512; // (beyond: 1024 threads per tile, 128 registers each — three systems do not fit)
 	uint64_t n0 = 1, M = L;
 	int mode = 6;
