@@ -5,10 +5,10 @@ CSRC := vkfft_amd/csrc
 LIBDIR := vkfft_amd/lib
 # --offload-compress: the gfx950 code objects are stored zstd-compressed in the library (165 MB -> a third) and unpacked by the HIP runtime when the module loads
 CXXFLAGS := -O3 -std=c++17 -fPIC -fvisibility=hidden -Iinclude -I$(CSRC) -Wno-unused-result --offload-compress
-# (the parts of the mixed-radix, cyclic-convolution and convolution-row registries: the lists VKFFT_MIXED_PARTS / VKFFT_MIXCONV_PARTS / VKFFT_MIX_CONV_ROWS_PARTS / VKFFT_MIX_CONV_COLS_PARTS of kernels.hip)
+# (the parts of the mixed-radix, cyclic-convolution and convolution-row registries: the lists VKFFT_MIXED_PARTS / VKFFT_MIXCONV_PARTS / VKFFT_MIX_CONV_ROWS_PARTS / VKFFT_MIX_CONV_COLS_PARTS / VKFFT_MIX_CONV_COLS_BANK_PARTS of kernels.hip)
 OBJS := $(foreach u,api planner kernels kernels_pow2 kernels_blue_r2r kernels_fused kernels_mixfused kernels_aux,build/obj/$(u).o) \
         $(foreach i,0 1 2 3 4 5 6 7 8 9 10 11 12 13 14 15 16 17 18 19,build/obj/kernels_mixed_$(i).o) $(foreach i,0 1 2 3 4 5,build/obj/kernels_mixconv_$(i).o) \
-        $(foreach i,0 1 2 3 4 5 6 7,build/obj/kernels_mixconv_rows_$(i).o) $(foreach i,0 1 2 3,build/obj/kernels_mixconv_cols_$(i).o) \
+        $(foreach i,0 1 2 3 4 5 6 7,build/obj/kernels_mixconv_rows_$(i).o) $(foreach i,0 1 2 3,build/obj/kernels_mixconv_cols_$(i).o) $(foreach i,0 1 2 3,build/obj/kernels_mixconv_cols_bank_$(i).o) \
         $(foreach t,f32_row f32_col f64_row f64_col,build/obj/kernels_opfft_$(t)_0.o build/obj/kernels_opfft_$(t)_1.o) build/obj/kernels_opfft_f32_col_2.o
 # the translation units that take longest to compile (12 minutes each for kernels_mixed_0 ... 5, 4-6 for the others; the rest 2 minutes or less), named first among the
 # library's prerequisites so that a parallel make starts them first and no core waits for one of them at the end; the link line keeps the order of OBJS

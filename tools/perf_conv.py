@@ -4,7 +4,8 @@ python tools/perf_conv.py rows: one-dimensional plans, the one-launch form (pow2
 launches) in the same process, alternating, on one buffer of 256 MiB; beside them the plain transform of the same rows (forward and normalised inverse in turn): the
 ceiling of a kernel that reads and writes the data once.
 python tools/perf_conv.py planes: 2-D / 3-D plans whose last axis is 7-smooth and no power of two, the merged last axis (mix_conv_col_kernel: three launches for a
-2-D plan) against VKFFT_MI355X_CONV_SEPARATE=1 (five) in the same process, alternating, on the same buffer."""
+2-D plan) against VKFFT_MI355X_CONV_SEPARATE=1 (five) in the same process, alternating, on the same buffer; and the bank cases, one input against numberKernels = K
+kernels (mix_conv_col_bank_kernel, pow2_col_blue_kernel MODE 9): one batch, a buffer of K systems."""
 import ctypes as C, json, os, sys, time
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, root)
@@ -57,15 +58,18 @@ def rows_ab(n, dp, r2c, pad, mib=256, rounds=7, it=10):
                 speedup=round(med["separate"] / med["fused"], 3), separate_spread=round((max(ms["separate"]) - min(ms["separate"])) / med["separate"], 3))
 
 
-def planes_ab(shape, dp, r2c, pad, mib=256, rounds=7, it=10):
-    """merged last axis against separate passes, timed like rows_ab.  shape: axis 0 first, the merged axis last; as many batches as fit `mib` (at least one)"""
+def planes_ab(shape, dp, r2c, pad, nk=1, mib=256, rounds=7, it=10):
+    """merged last axis against separate passes, timed like rows_ab.  shape: axis 0 first, the merged axis last; as many batches as fit `mib` (at least one).
+    nk > 1: a bank of nk kernels, ONE batch (the library takes no bank together with several batches) in a buffer of nk systems, whatever its size"""
     es = 16 if dp else 8
     elems = (shape[0] // 2 + 1 if r2c else shape[0]) * int(np.prod(shape[1:]))
-    nb = max(1, (mib << 20) // (elems * es))
+    nb = max(1, (mib << 20) // (elems * es)) if nk == 1 else 1
     rt = torch.float64 if dp else torch.float32
-    data = torch.rand(2 * elems * nb, device="cuda", dtype=rt)
-    kern = torch.zeros(2 * elems, device="cuda", dtype=rt); kern[0::2] = 1
+    data = torch.rand(2 * elems * nb * nk, device="cuda", dtype=rt)
+    kern = torch.zeros(2 * elems * nk, device="cuda", dtype=rt); kern[0::2] = 1
     kw = dict(buffer_ptr=data.data_ptr(), kernel=kern.data_ptr(), performConvolution=1, dp=dp, r2c=r2c, normalize=True)
+    if nk > 1:
+        kw.update(numberKernels=nk)
     last = len(shape) - 1
     if pad:
         flag = [0] * 4; left = [0] * 4; right = [0] * 4
@@ -95,8 +99,8 @@ def planes_ab(shape, dp, r2c, pad, mib=256, rounds=7, it=10):
             ms[k].append(e0.elapsed_time(e1) / it)
     for a in apps.values(): a.delete()
     med = {k: float(np.median(v)) for k, v in ms.items()}
-    moved = 2 * nb * elems * es  # one read and one write of the data (the padded half included: the other axes visit it)
-    return dict(shape=list(shape), dp=dp, r2c=r2c, zero_padded_upper_half_of_last_axis=bool(pad), batches=nb, launches={k: v[0] for k, v in info.items()}, merged_kernels=names,
+    moved = (1 + nk) * nb * elems * es  # one read of the data and one write per result (the padded half included: the other axes visit it)
+    return dict(shape=list(shape), dp=dp, r2c=r2c, zero_padded_upper_half_of_last_axis=bool(pad), batches=nb, kernels=nk, buffer_MiB=round(nb * nk * elems * es / 2**20, 1), launches={k: v[0] for k, v in info.items()}, merged_kernels=names,
                 ms={k: round(v, 4) for k, v in med.items()}, ms_min_max={k: [round(min(v), 4), round(max(v), 4)] for k, v in ms.items()},
                 merged_alg_GBps=round(moved / med["merged"] / 1e6, 1), separate_alg_GBps=round(moved / med["separate"] / 1e6, 1),
                 speedup=round(med["separate"] / med["merged"], 3), separate_spread=round((max(ms["separate"]) - min(ms["separate"])) / med["separate"], 3))
@@ -107,6 +111,13 @@ if len(sys.argv) > 1 and sys.argv[1] == "planes":
     for shape, dp, r2c, pad in [((1920, 1080), False, False, False), ((1000, 1000), False, False, False), ((360, 360, 360), False, False, False), ((360, 360, 360), False, True, False),
                                 ((1024, 1536), False, False, False), ((480, 500), True, False, False), ((1920, 1080), False, False, True)]:
         print(json.dumps(planes_ab(shape, dp, r2c, pad)), flush=True)
+    # banks of kernels.  Last axes of 1080 and 1000 points have no bank instance (tools/gen_mix_conv_col_bank_table.py, DROPPED): both sides run the separate passes
+    for shape, dp, r2c, pad, nk in [((1920, 1080), False, False, False, 2), ((1920, 1080), False, False, False, 8), ((1000, 1000), False, False, False, 4), ((360, 360, 360), False, True, False, 2),
+                                    ((480, 500), True, False, False, 4), ((1024, 1024), False, False, False, 4), ((1920, 1080), False, False, True, 4),
+                                    # the classes the cases above leave out (fp32 tiles of 8 / 16 / 32 columns on lengths that have an instance, a second fp64 length, the power-of-two form in fp64)
+                                    ((1920, 1200), False, False, False, 2), ((1920, 1200), False, False, False, 8), ((1920, 1200), False, False, True, 4), ((1000, 720), False, False, False, 4),
+                                    ((1000, 120), False, False, False, 4), ((480, 120), True, False, False, 4), ((1024, 1024), True, False, False, 4)]:
+        print(json.dumps(planes_ab(shape, dp, r2c, pad, nk)), flush=True)
     sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "rows":
     print(json.dumps(dict(source_hash=api.source_hash(), library_is_current=api.library_is_current(), device=torch.cuda.get_device_name(0))), flush=True)

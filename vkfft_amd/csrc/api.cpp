@@ -532,7 +532,8 @@ VkFFTResult initialize_convolution(VkFFTApplication* app, const VkFFTConfigurati
 	if (nk > 1 && in.bufferSize) b.bufferSize = in.bufferSize;
 	// merged last axis (the reference's convolution-merged kernel, vkFFT_Convolution.h:125): when a one-pass merged kernel exists for that axis
 	// the two sub-applications omit it
-	if (in.FFTdim >= 2 && nk == 1 && !in.crossPowerSpectrumNormalization && !in.frequencyZeroPadding && !in.isInputFormatted && !sw.convSeparate) {
+	// (a bank of numberKernels > 1 kernels, one batch: the bank instances transform the input once and run product -> inverse -> store per kernel)
+	if (in.FFTdim >= 2 && !in.crossPowerSpectrumNormalization && !in.frequencyZeroPadding && !in.isInputFormatted && !sw.convSeparate) {
 		TransformDesc d;
 		d.fftDim = (int)in.FFTdim;
 		for (int i = 0; i < 4; i++) d.size[i] = in.size[i] ? in.size[i] : 1;
@@ -550,6 +551,7 @@ VkFFTResult initialize_convolution(VkFFTApplication* app, const VkFFTConfigurati
 		cd.matrix = (uint32_t)m; cd.coordinates = (uint32_t)c.coordinateFeatures; cd.symmetric = in.symmetricKernel ? 1u : 0u; cd.conjugate = (uint32_t)in.conjugateConvolution;
 		cd.kernelSystems = m > 1 ? (in.symmetricKernel ? m * (m + 1) / 2 : m * m) : c.coordinateFeatures;
 		cd.scale = in.normalize ? 1.0 / (double)d.size[in.FFTdim - 1] : 1.0;
+		cd.numKernels = (uint32_t)nk;
 		VkFFTPlan* pl = (VkFFTPlan*)calloc(1, sizeof(VkFFTPlan));
 		DirectionPlan* dpl = new (std::nothrow) DirectionPlan();
 		if (pl && dpl) {
@@ -561,7 +563,11 @@ VkFFTResult initialize_convolution(VkFFTApplication* app, const VkFFTConfigurati
 				st->convMid = pl;
 				st->convInvFullCfg = b;
 				f.omitDimension[in.FFTdim - 1] = 1; b.omitDimension[in.FFTdim - 1] = 1;
-				if (in.printMemoryLayout || sw.printPlan) fprintf(stderr, "[vkfft_mi355x] convolution: axis %d merged (forward, %ux%u kernel product, inverse in one pass of %s)\n", (int)in.FFTdim - 1, cd.matrix, cd.matrix, kernel_kind_name(dpl->passes[dpl->passes.size() / 2].kernel).global);
+				if (in.printMemoryLayout || sw.printPlan) {
+					char bank[96] = "";
+					if (cd.numKernels > 1) snprintf(bank, sizeof(bank), "; %u kernels: one forward transform, product and inverse per kernel", cd.numKernels);
+					fprintf(stderr, "[vkfft_mi355x] convolution: axis %d merged (forward, %ux%u kernel product, inverse in one pass of %s%s)\n", (int)in.FFTdim - 1, cd.matrix, cd.matrix, kernel_kind_name(dpl->passes[dpl->passes.size() / 2].kernel).global, bank);
+				}
 			} else free_direction(pl);
 		} else { free(pl); delete dpl; }
 	}

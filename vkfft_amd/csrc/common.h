@@ -183,6 +183,10 @@ struct PassParams {
 	uint32_t convM, convCf, convSymmetric, convConj;
 	int64_t convSysStride, convKerStride1, convKerStride2;
 	int64_t convKerStrideJ, convKerSysStride; // kernel strides along the axis and between kernel systems (they differ from the data's when the data sits in the Four-Step scratch)
+	// a bank of convNk > 1 kernels (numberKernels; the bank forms of the merged pass): the input is transformed once, result f of every system lies convBankStride
+	// elements behind result f - 1, kernel f's spectra convKerBankStride elements behind kernel f - 1's (the layouts of conv_pointwise_kernel); 0 / 1: no bank
+	int64_t convBankStride, convKerBankStride;
+	uint32_t convNk;
 };
 
 // index of kernel component (j, l) among the systems of one convolution kernel.  symmetricKernel: the packed upper triangle in the DOCUMENTED order

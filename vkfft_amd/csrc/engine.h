@@ -13,16 +13,16 @@ namespace vkfft_mi355x {
 
 // ROLE_TEMP2: a second scratch region behind ROLE_TEMP in the same allocation, for plans that wrap an inner plan which uses ROLE_TEMP itself
 enum BufRole : int { ROLE_BUFFER = 0, ROLE_TEMP = 1, ROLE_INPUT = 2, ROLE_OUTPUT = 3, ROLE_TEMP2 = 4 };
-enum KernelKind : int { KERNEL_GENERIC = 0, KERNEL_POW2_ROW = 1, KERNEL_POW2_COL = 2, KERNEL_R2C_PAIR = 3, KERNEL_MIXED_ROW = 5, KERNEL_OPFFT = 6, KERNEL_POW2_BLUE = 7, KERNEL_POW2_COL_BLUE = 8, KERNEL_POW2_BLUE_R2R = 9, KERNEL_POW2_FUSED = 10, KERNEL_TRANSPOSE = 11, KERNEL_REAL_MAP = 12, KERNEL_MIXCONV = 13, KERNEL_MIX_FUSED = 14, KERNEL_POW2_CONV_ROW = 15, KERNEL_MIX_CONV_ROW = 16, KERNEL_MIX_CONV_COL = 17 };
+enum KernelKind : int { KERNEL_GENERIC = 0, KERNEL_POW2_ROW = 1, KERNEL_POW2_COL = 2, KERNEL_R2C_PAIR = 3, KERNEL_MIXED_ROW = 5, KERNEL_OPFFT = 6, KERNEL_POW2_BLUE = 7, KERNEL_POW2_COL_BLUE = 8, KERNEL_POW2_BLUE_R2R = 9, KERNEL_POW2_FUSED = 10, KERNEL_TRANSPOSE = 11, KERNEL_REAL_MAP = 12, KERNEL_MIXCONV = 13, KERNEL_MIX_FUSED = 14, KERNEL_POW2_CONV_ROW = 15, KERNEL_MIX_CONV_ROW = 16, KERNEL_MIX_CONV_COL = 17, KERNEL_MIX_CONV_COL_BANK = 18 };
 // the names of a kind: as the print-plan lines show it, and its __global__ function (vkfftMI355XDescribePlan); 4 is no kind
 struct KernelKindName { const char* brief; const char* global; };
 inline constexpr KernelKindName kKernelKindNames[] = {
 	{"generic", "generic_pass_kernel"}, {"pow2_row", "pow2_row_kernel"}, {"pow2_col", "pow2_col_kernel"}, {"r2c_pair", "r2c_even_pair_kernel"}, {"?", "?"}, {"mixed_row", "mixed_row_kernel"},
 	{"opfft", "opfft_kernel"}, {"pow2_blue", "pow2_blue_kernel"}, {"pow2_col_blue", "pow2_col_blue_kernel"}, {"pow2_blue_r2r", "pow2_blue_r2r_kernel"}, {"pow2_fused", "pow2_fused_kernel"},
 	{"transpose", "transpose_kernel"}, {"real_map", "real_map_kernel"}, {"mixconv", "mixconv_kernel"}, {"mix_fused", "mix_fused_kernel"}, {"pow2_conv_row", "pow2_conv_row_kernel"},
-	{"mix_conv_row", "mix_conv_row_kernel"}, {"mix_conv_col", "mix_conv_col_kernel"}};
+	{"mix_conv_row", "mix_conv_row_kernel"}, {"mix_conv_col", "mix_conv_col_kernel"}, {"mix_conv_col_bank", "mix_conv_col_bank_kernel"}};
 constexpr int kNumKernelKinds = (int)(sizeof(kKernelKindNames) / sizeof(kKernelKindNames[0]));
-static_assert(kNumKernelKinds == KERNEL_MIX_CONV_COL + 1, "one name per KernelKind, the last enumerator included");
+static_assert(kNumKernelKinds == KERNEL_MIX_CONV_COL_BANK + 1, "one name per KernelKind, the last enumerator included");
 inline const KernelKindName& kernel_kind_name(int kind) { return kKernelKindNames[kind >= 0 && kind < kNumKernelKinds ? kind : 4]; }
 
 struct HostDim {
@@ -104,7 +104,9 @@ int build_direction_plan(const TransformDesc& d, DirectionPlan& out);
 // system, kernel matrix product per frequency, inverse transform (pow2_col_blue_kernel MODE 6; reference vkFFT_Convolution.h:125, vkFFT_RunApp.h:235-345).
 // A 7-smooth last axis that is no power of two, 12 ... 2048 points (fp64: ... 512), without a kernel matrix: one pass of mix_conv_col_kernel (kernel_mix_conv_col.h).
 // d.batch = numberBatches (NOT folded with the coordinates); returns 3002 when no such pass exists for the shape (the caller keeps separate passes)
-struct ConvAxisDesc { uint32_t matrix = 1, coordinates = 1, symmetric = 0, conjugate = 0; double scale = 1.0; uint64_t kernelSystems = 1; };
+// numKernels > 1: a bank of kernels, one input and numKernels results (d.batch = 1): the bank instances (pow2_col_blue_kernel MODE 9 / 10 on the non-split
+// power-of-two lengths, mix_conv_col_bank_kernel on the 7-smooth ones, there without a kernel matrix); 3002 where none exists
+struct ConvAxisDesc { uint32_t matrix = 1, coordinates = 1, symmetric = 0, conjugate = 0; double scale = 1.0; uint64_t kernelSystems = 1; uint32_t numKernels = 1; };
 int build_conv_axis_plan(const TransformDesc& d, const ConvAxisDesc& c, DirectionPlan& out);
 // One-launch convolution of a ONE-dimensional plan: forward transform, product with the row's kernel spectrum, inverse transform.  Unit-stride power-of-two rows
 // (pow2_conv_row_kernel in kernel_pow2_conv.h, in registers) or 7-smooth rows of 100 ... 4096 points (mix_conv_row_kernel in kernel_mix_conv.h, through one LDS row).
@@ -182,6 +184,9 @@ int launch_mix_conv_row(const PassPlan& pp, const PassParams& prm, hipStream_t s
 // merged convolution along a strided last axis of a 7-smooth length that is no power of two (kernel_mix_conv_col.h): tiles of perWg neighbouring columns
 KernelShape mix_conv_col_lookup(uint64_t n, bool dp);
 int launch_mix_conv_col(const PassPlan& pp, const PassParams& prm, hipStream_t stream);
+// ... and its bank form (kernel_mix_conv_col_bank.h): one input against numberKernels kernels, the spectrum of the tile kept in registers
+KernelShape mix_conv_col_bank_lookup(uint64_t n, bool dp);
+int launch_mix_conv_col_bank(const PassPlan& pp, const PassParams& prm, hipStream_t stream);
 bool mixrad_available(int variant); // the Rader row instance also exists as a stage of composite lengths (kernel_mixrad.h)
 // ... its buffer pitch (elements), stage-twiddle count and thread groups of the wave-aligned layout (0: not offered); ok: mixrad_available(variant)
 struct MixradShape { bool ok = false; int sp = 0, lutn = 0, groups = 0, groupsDense = 0; };

@@ -405,11 +405,14 @@ __global__ void __launch_bounds__(((1 << SCH::LOGN) >> SCH::LOGE) * TC) pow2_col
 			if (sc != (T)1) y = cscale(y, sc);
 			gb_store<T>(gout, (pos < n && !(pos - p.padOutL < p.padOutN)) ? laneOut : kGbInvalid, m * stepOut, y);
 		}
-	} else if constexpr (MODE == 6 || MODE == 7) { // (7: the narrow-tile instance of 1024 points whose 512 threads have the registers for a kernel matrix)
+	} else if constexpr (MODE == 6 || MODE == 7 || MODE == 9 || MODE == 10) { // (7: the narrow-tile instance of 1024 points whose 512 threads have the registers for a kernel matrix)
 		// Merged convolution along this (strided) axis — the reference's convolution-merged last axis (vkFFT_Convolution.h:125-447, vkFFT_RunApp.h:235-345):
 		// column FFT of every coordinate system -> per frequency the kernel matrix times the vector of coordinates -> inverse column FFT of every
 		// result (swap identity), in place.  One trip through memory instead of three (last forward pass, element-wise product, first inverse pass).
+		// MODE 9 / 10: the bank forms of 6 / 7 (numberKernels = convNk > 1, one batch): the spectra w[l][m] are kept and product -> inverse -> store runs once per
+		// kernel, from the last kernel to the first: result 0 replaces the input, which this workgroup alone reads, and only once (conv_pointwise_kernel's order)
 		constexpr int MAXM = 3;
+		constexpr bool BANK = MODE == 9 || MODE == 10;
 		const uint32_t mm = p.convM, cf = p.convCf;
 		const uint32_t lane = valid ? (tau * (uint32_t)p.inStrideJ + c * (uint32_t)p.dim[0].inStride) * ES : kGbInvalid;
 		const uint32_t step = (uint32_t)(TPF * (uint32_t)p.inStrideJ) * ES;
@@ -431,39 +434,49 @@ __global__ void __launch_bounds__(((1 << SCH::LOGN) >> SCH::LOGE) * TC) pow2_col
 			}
 		}
 		const bool kconj = p.convConj == 2;
+		uint32_t fk = BANK ? p.convNk : 1u;
+		do {
+			--fk;
+			// both resources are re-based per kernel in 64 bits: the spans the planner checked are those of ONE result and ONE kernel
+			const int64_t outF = [&] { if constexpr (BANK) return outB + (int64_t)fk * p.convBankStride; else return outB; }();
+			const GBuf gkf = [&] {
+				if constexpr (BANK) return make_gbuf((const cx<T>*)p.aux2 + ((int64_t)g1 * p.convKerStride1 + (int64_t)g2 * p.convKerStride2 + (int64_t)col0 + (int64_t)fk * p.convKerBankStride));
+				else return gker;
+			}();
 #pragma unroll
-		for (int j = 0; j < MAXM; j++) {
-			if ((uint32_t)j < cf) {
-				cx<T> acc[E];
-				if (mm <= 1) {
-					const uint32_t ks = (uint32_t)((int64_t)j * p.convKerSysStride) * ES; // (the kernel systems lie within the 2 GiB span of the resource: planner)
+			for (int j = 0; j < MAXM; j++) {
+				if ((uint32_t)j < cf) {
+					cx<T> acc[E];
+					if (mm <= 1) {
+						const uint32_t ks = (uint32_t)((int64_t)j * p.convKerSysStride) * ES; // (the kernel systems lie within the 2 GiB span of the resource: planner)
 #pragma unroll
-					for (int m = 0; m < E; m++) { cx<T> k = gb_load<T>(gker, klane, m * kstep + ks); if (kconj) k = cconj(k); acc[m] = cmul(k, w[j][m]); }
-				} else {
+						for (int m = 0; m < E; m++) { cx<T> k = gb_load<T>(gkf, klane, m * kstep + ks); if (kconj) k = cconj(k); acc[m] = cmul(k, w[j][m]); }
+					} else {
 #pragma unroll
-					for (int m = 0; m < E; m++) acc[m] = cx<T>{(T)0, (T)0};
+						for (int m = 0; m < E; m++) acc[m] = cx<T>{(T)0, (T)0};
 #pragma unroll
-					for (int l = 0; l < MAXM; l++) {
-						if ((uint32_t)l < mm) {
-							const uint32_t ks = (uint32_t)((int64_t)conv_kernel_index((uint32_t)j, (uint32_t)l, mm, p.convSymmetric != 0) * p.convKerSysStride) * ES;
+						for (int l = 0; l < MAXM; l++) {
+							if ((uint32_t)l < mm) {
+								const uint32_t ks = (uint32_t)((int64_t)conv_kernel_index((uint32_t)j, (uint32_t)l, mm, p.convSymmetric != 0) * p.convKerSysStride) * ES;
 #pragma unroll
-							for (int m = 0; m < E; m++) { cx<T> k = gb_load<T>(gker, klane, m * kstep + ks); if (kconj) k = cconj(k); acc[m] = cadd(acc[m], cmul(k, w[l][m])); }
+								for (int m = 0; m < E; m++) { cx<T> k = gb_load<T>(gkf, klane, m * kstep + ks); if (kconj) k = cconj(k); acc[m] = cadd(acc[m], cmul(k, w[l][m])); }
+							}
 						}
 					}
-				}
 #pragma unroll
-				for (int m = 0; m < E; m++) acc[m] = cswap(acc[m]);
-				if constexpr (SCH::NS > 1) VKFFT_SYNC();
-				pow2_stages<T, SCH, 0, TPF, TCP, TwGlobal<T>>(acc, lds + c, TwGlobal<T>{glut}, tau, false);
-				const GBuf go = make_gbuf((cx<T>*)p.out + (outB + (int64_t)j * p.convSysStride));
+					for (int m = 0; m < E; m++) acc[m] = cswap(acc[m]);
+					if constexpr (SCH::NS > 1) VKFFT_SYNC();
+					pow2_stages<T, SCH, 0, TPF, TCP, TwGlobal<T>>(acc, lds + c, TwGlobal<T>{glut}, tau, false);
+					const GBuf go = make_gbuf((cx<T>*)p.out + (outF + (int64_t)j * p.convSysStride));
 #pragma unroll
-				for (int m = 0; m < E; m++) {
-					cx<T> y = cswap(acc[m]);
-					if (sc != (T)1) y = cscale(y, sc);
-					gb_store<T>(go, (tau + (uint32_t)(m * TPF) - p.padOutL < p.padOutN) ? kGbInvalid : lane, m * step, y);
+					for (int m = 0; m < E; m++) {
+						cx<T> y = cswap(acc[m]);
+						if (sc != (T)1) y = cscale(y, sc);
+						gb_store<T>(go, (tau + (uint32_t)(m * TPF) - p.padOutL < p.padOutN) ? kGbInvalid : lane, m * step, y);
+					}
 				}
 			}
-		}
+		} while (BANK && fk > 0);
 	} else if constexpr (MODE == 8) {
 		// the FIRST pass of a strided two-pass (Four-Step) transform run backwards, scratch -> data: conj twiddle w^(-k * column), inverse column FFT
 		// (closes the merged convolution of a long strided axis: forward pass A, merged pass on the inner factor, this pass)

@@ -36,6 +36,8 @@ int launch_pass(const PassPlan& pp, const PassParams& prm, hipStream_t stream) {
 		return launch_mix_conv_row(pp, prm, stream);
 	case KERNEL_MIX_CONV_COL:
 		return launch_mix_conv_col(pp, prm, stream);
+	case KERNEL_MIX_CONV_COL_BANK:
+		return launch_mix_conv_col_bank(pp, prm, stream);
 	case KERNEL_TRANSPOSE:
 		return launch_transpose(pp, prm, stream);
 	case KERNEL_REAL_MAP:
@@ -230,6 +232,33 @@ int launch_mix_conv_col(const PassPlan& pp, const PassParams& prm, hipStream_t s
 	return launch_on_grid((uint64_t)prm.tilesPerG0 * prm.dim[1].count * prm.dim[2].count, pp.variant >= 0 && idx < cnt ? tab[idx].launch : nullptr, prm, stream);
 }
 
+// ---- ... and its bank form (numberKernels > 1): four table parts (kernels_mixconv_cols_bank_*.hip), the entries of the same record -----
+#define VKFFT_MIX_CONV_COLS_BANK_PARTS(X, V, f) X(V, f, 0) X(V, f, 1) X(V, f, 2) X(V, f, 3)
+VKFFT_REGISTRY_PARTS(MixConvColVariant, mix_conv_cols_bank, kMixConvColsBankParts, VKFFT_MIX_CONV_COLS_BANK_PARTS)
+static const MixConvColVariant* mix_conv_cols_bank_part(int part, int* count) {
+	return part < 0 ? nullptr : mix_conv_cols_bank_part_fns[part % kMixConvColsBankParts](count);
+}
+KernelShape mix_conv_col_bank_lookup(uint64_t n, bool dp) {
+	for (int part = 0; part < kMixConvColsBankParts; part++) {
+		int cnt = 0;
+		const MixConvColVariant* tab = mix_conv_cols_bank_part(part, &cnt);
+		for (int i = 0; i < cnt; i++) {
+			if ((uint64_t)tab[i].n != n || tab[i].dp != dp) continue;
+			KernelShape k;
+			k.variant = (part << 16) | i; k.perWg = tab[i].tc; k.threads = tab[i].tpf * tab[i].tc;
+			for (int r = 0; r < 5; r++) k.sched[r] = tab[i].rad[r];
+			return k;
+		}
+	}
+	return {};
+}
+int launch_mix_conv_col_bank(const PassPlan& pp, const PassParams& prm, hipStream_t stream) {
+	int cnt = 0;
+	const MixConvColVariant* tab = mix_conv_cols_bank_part((pp.variant >> 16) % kMixConvColsBankParts, &cnt);
+	const int idx = pp.variant & 0xffff;
+	return launch_on_grid((uint64_t)prm.tilesPerG0 * prm.dim[1].count * prm.dim[2].count, pp.variant >= 0 && idx < cnt ? tab[idx].launch : nullptr, prm, stream);
+}
+
 // ---- op-FFT registry: nine table parts, one translation unit each (kernels_opfft_*.hip) ---------------------------
 #define VKFFT_OPFFT_PARTS(X, V, f) X(V, f, f32_row_0) X(V, f, f32_row_1) X(V, f, f32_col_0) X(V, f, f32_col_1) X(V, f, f64_row_0) X(V, f, f64_row_1) X(V, f, f64_col_0) X(V, f, f64_col_1) \
 	X(V, f, f32_col_2) /* part 8: tools/gen_opfft_col_extra.py */
@@ -241,6 +270,7 @@ static const OpfftVariant* opfft_part(int part, int* count) { // part = 2 * ((dp
 #undef VKFFT_PART_REF
 #undef VKFFT_PART_DECL
 #undef VKFFT_OPFFT_PARTS
+#undef VKFFT_MIX_CONV_COLS_BANK_PARTS
 #undef VKFFT_MIX_CONV_COLS_PARTS
 #undef VKFFT_MIX_CONV_ROWS_PARTS
 #undef VKFFT_MIXCONV_PARTS

@@ -192,6 +192,12 @@ static const Pow2ColBlueVariant kPow2ColBlueVariants[] = {
 	VKFFT_P2CB(double, true, 3, 3, 2, 0, 16),
 	VKFFT_P2CB(double, true, 3, 3, 3, 0, 8),
 	VKFFT_P2CB(double, true, 4, 3, 3, 0, 8),
+	// the bank forms (numberKernels > 1) of the merged convolution, MODE 9 of the MODE 6 instances and MODE 10 of the two MODE 7 ones; behind the others: their indices stay.
+	// 1024 points in fp32 and 512 in fp64 have the MODE 10 instance only: the planner takes the narrow tile for every bank of that length (MODE 9 on 16 x 1024 points spills 768 bytes per lane)
+	VKFFT_P2CB1(float, false, 3, 3, 0, 0, 32, 9), VKFFT_P2CB1(float, false, 4, 3, 0, 0, 32, 9), VKFFT_P2CB1(float, false, 4, 4, 0, 0, 32, 9),
+	VKFFT_P2CB1(float, false, 4, 3, 2, 0, 16, 9), VKFFT_P2CB1(float, false, 4, 3, 3, 0, 8, 10),
+	VKFFT_P2CB1(double, true, 3, 3, 0, 0, 16, 9), VKFFT_P2CB1(double, true, 3, 2, 2, 0, 16, 9), VKFFT_P2CB1(double, true, 3, 3, 2, 0, 16, 9),
+	VKFFT_P2CB1(double, true, 4, 3, 3, 0, 8, 9), VKFFT_P2CB1(double, true, 3, 3, 3, 0, 8, 10),
 };
 constexpr int kNumPow2ColBlueVariants = (int)(sizeof(kPow2ColBlueVariants) / sizeof(kPow2ColBlueVariants[0]));
 

@@ -17,6 +17,10 @@ namespace vkfft_mi355x {
 template <typename T, int R> struct McRegs { const cx<T> (*x)[R]; };
 template <typename X> struct McIsRegs { static constexpr bool value = false; };
 template <typename T, int R> struct McIsRegs<McRegs<T, R>> { static constexpr bool value = true; };
+// OUT = McRegSink: the outputs of the last stage stay in registers (y[b][k] = output tau + b * TPF + k * S of the last stage, S its stride), kept by the caller
+template <typename T, int R> struct McRegSink { cx<T> (*y)[R]; };
+template <typename X> struct McIsRegSink { static constexpr bool value = false; };
+template <typename T, int R> struct McIsRegSink<McRegSink<T, R>> { static constexpr bool value = true; };
 template <typename T, typename SCH, int SI, int TPF, int LS, bool PADDED, bool SF, bool SL, typename IN, typename OUT>
 __device__ inline void mc_stage(cx<T>* ldsf, const GBuf glut, const uint32_t tau, const bool waveOnly, const IN& in, const OUT& out) {
 	constexpr int N = SCH::N, R = SCH::rad[SI], NB = N / R, P = (NB + TPF - 1) / TPF, S = SCH::S(SI);
@@ -54,7 +58,10 @@ __device__ inline void mc_stage(cx<T>* ldsf, const GBuf glut, const uint32_t tau
 			dft<R, T>(x[b]);
 			if constexpr (last) {
 #pragma unroll
-				for (int k = 0; k < R; k++) out(t, (uint32_t)(k * S), x[b][k]); // last stage: s = t
+				for (int k = 0; k < R; k++) { // last stage: s = t
+				if constexpr (McIsRegSink<OUT>::value) out.y[b][k] = x[b][k];
+				else out(t, (uint32_t)(k * S), x[b][k]);
+			}
 			} else {
 				const uint32_t ob = (t - s) * (uint32_t)R + s;
 #pragma unroll

@@ -2403,7 +2403,9 @@ static int build_conv_axis_mixed(const TransformDesc& d, const ConvAxisDesc& c, 
 	const bool dp = d.dp;
 	const uint64_t es = dp ? 16 : 8;
 	if (c.matrix > 1 || c.coordinates < 1 || c.conjugate > 2) return 3002;
-	const KernelShape ks = mix_conv_col_lookup(L, dp);
+	const bool bank = c.numKernels > 1; // one input, numKernels results: mix_conv_col_bank_kernel, where its table holds the length (one batch: api.cpp)
+	if (bank && d.batch != 1) return 3002;
+	const KernelShape ks = bank ? mix_conv_col_bank_lookup(L, dp) : mix_conv_col_lookup(L, dp);
 	if (!ks) return 3002;
 	const int64_t strideJ = (int64_t)d.bufStride[a - 1], sys = (int64_t)d.bufStride[nd - 1];
 	const uint64_t W = d.kind == 1 ? d.size[0] / 2 + 1 : d.size[0];
@@ -2437,7 +2439,8 @@ static int build_conv_axis_mixed(const TransformDesc& d, const ConvAxisDesc& c, 
 	q.scale = c.scale;
 	if (d.padR[a] > d.padL[a]) { q.padInL = q.padOutL = (uint32_t)d.padL[a]; q.padInN = q.padOutN = (uint32_t)(d.padR[a] - d.padL[a]); }
 	pp.lutOff = build_mix_stage_lut(ar, ks.sched, dp);
-	pp.kernel = KERNEL_MIX_CONV_COL; pp.variant = ks.variant; pp.threads = (uint32_t)ks.threads; pp.dp = dp; pp.auxIsKernel = true;
+	if (bank) { q.convNk = c.numKernels; q.convBankStride = (int64_t)cf * sys; q.convKerBankStride = (int64_t)c.kernelSystems * sys; } // (conv_pointwise_kernel's layouts)
+	pp.kernel = bank ? KERNEL_MIX_CONV_COL_BANK : KERNEL_MIX_CONV_COL; pp.variant = ks.variant; pp.threads = (uint32_t)ks.threads; pp.dp = dp; pp.auxIsKernel = true;
 	pp.inRole = pp.outRole = ROLE_BUFFER; pp.inElemBytes = pp.outElemBytes = (int)es;
 	pp.label = "convolution";
 	out.passes.push_back(pp);
@@ -2459,15 +2462,19 @@ int build_conv_axis_plan(const TransformDesc& d, const ConvAxisDesc& c, Directio
 	const uint64_t matrixCap = dp ? 256 : 512; // (beyond: 1024 threads per tile, 128 registers each — three systems do not fit)
 	uint64_t n0 = 1, M = L;
 	int mode = 6;
-	if (c.matrix > 1 && L == 2 * matrixCap && pow2_col_blue_lookup(ilog2(L), dp, 7)) mode = 7; // (the narrow-tile instance)
+	// (the narrow-tile instance; a bank of kernels takes it at that length without a matrix too: at 1024 threads the retained spectra spill, 768 bytes per lane in fp32)
+	if ((c.matrix > 1 || c.numKernels > 1) && L == 2 * matrixCap && pow2_col_blue_lookup(ilog2(L), dp, 7)) mode = 7;
 	if (L > 1024 || (c.matrix > 1 && L > matrixCap && mode == 6)) { // two factors, the inner one as large as a merged kernel allows
+		if (c.numKernels > 1) return 3002; // (a bank of kernels: the non-split form only)
 		if (padded) return 3002; // (the passes of a split axis address by factor, not by the natural index the padded range is given in)
 		M = c.matrix > 1 ? matrixCap : 1024;
 		while (M > 64 && L / M < 64) M >>= 1;
 		n0 = L / M;
 		if (n0 < 64 || n0 > 1024 || M < 64) return 3002;
 	}
-	const KernelShape ks = pow2_col_blue_lookup(ilog2(M), dp, mode);
+	const bool bank = c.numKernels > 1; // the bank forms of MODE 6 / 7: MODE 9 / 10 (one batch: api.cpp)
+	if (bank && d.batch != 1) return 3002;
+	const KernelShape ks = pow2_col_blue_lookup(ilog2(M), dp, bank ? mode + 3 : mode);
 	if (!ks) return 3002;
 	const int64_t strideJ = (int64_t)d.bufStride[a - 1], sys = (int64_t)d.bufStride[nd - 1];
 	const uint64_t W = d.kind == 1 ? d.size[0] / 2 + 1 : d.size[0];
@@ -2505,6 +2512,7 @@ int build_conv_axis_plan(const TransformDesc& d, const ConvAxisDesc& c, Directio
 		for (int i = 0; i < 3; i++) q.dim[i] = {(uint32_t)dims[i].count, dims[i].inStride, dims[i].outStride};
 		q.convKerStride1 = kstr[1]; q.convKerStride2 = kstr[2]; q.convKerSysStride = sys;
 		q.convM = c.matrix; q.convCf = c.coordinates; q.convSymmetric = c.symmetric; q.convConj = c.conjugate;
+		if (bank) { q.convNk = c.numKernels; q.convBankStride = (int64_t)c.coordinates * sys; q.convKerBankStride = (int64_t)c.kernelSystems * sys; } // (conv_pointwise_kernel's layouts)
 		q.tilesPerG0 = (uint32_t)((W + (uint64_t)ks.perWg - 1) / (uint64_t)ks.perWg);
 		q.scale = split ? 1.0 : c.scale;
 		if (padded) { q.padInL = q.padOutL = (uint32_t)d.padL[a]; q.padInN = q.padOutN = (uint32_t)(d.padR[a] - d.padL[a]); } // (spatial padding: read side of the forward half, write side of the inverse half)
